@@ -1,6 +1,6 @@
 """bench.py — TimeViper-9B long-video forward (prefill) on N MI355X, synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames T] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of `GenericTimeViperVLM.forward` (ViT over 256-frame clips, eight per launch ->
@@ -9,6 +9,12 @@ pdrop -> last-token logits) over T frames that are already resident in HBM.  Wit
 the frame/token sequence is sharded over the ranks (timeviper_amd.distributed; frame ranges sized so
 that causal attention does not leave the last rank behind) and the total work is fixed
 ("scaling": "strong").  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline figure (`value`, `ms_per_step`); with
+--dump-outputs DIR it also writes the last timed step's logits to DIR/logits.npy (float32; inputs and weights are
+seeded and the timed path repeats bit for bit, so two builds can be compared output for output).  --full adds everything
+below: per-operator event timers inside the timed steps (`roofline`, `rooflines`, `timed_ms_per_step`), the copy rate of
+this box and the CPU baseline.
 
 roofline: the SSD selective-scan kernel — algorithmic bytes (45 312 B per
 token per Mamba layer at Nano dims, bf16) / its launch durations measured live with
@@ -21,6 +27,7 @@ timed on this box's host cores on a bounded sample and scaled to frames/s.
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -660,6 +667,22 @@ class CudaEnv:
                           "729->16 + 56-layer Nemotron-Nano-9B-v2 hybrid (27 Mamba2 / 25 MLP / 4 attention), {L} tokens, batch 1")
 
 
+def dump_outputs(dirname, arrays, limit_bytes=64 << 20):
+    """DIR/<name>.npy for every output of the last timed step, as float32 (bf16 / fp16 widened, fp64 kept)."""
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > limit_bytes:
+        raise ValueError(f"--dump-outputs: {total} bytes of outputs, more than {limit_bytes}")
+    for name, a in host.items():
+        np.save(d / f"{name}.npy", a)
+
+
 def launch_children(script: str, argv, gpus: int) -> int:
     """`python bench.py --gpus N` typed by hand: start the N ranks as a CHILD job (one process per GPU,
     torch.distributed.run) and relay its output and exit code.  Nothing has touched the GPU in this process yet
@@ -682,7 +705,12 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--frames", type=int, default=int(os.environ.get("TV_BENCH_FRAMES", 10240)))
     ap.add_argument("--no-pdrop", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-operator rooflines (event timers inside the timed steps), the copy rate and the "
+                         "CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the last-token logits) to DIR/logits.npy, float32")
     ap.add_argument("--config", default="0",
                     help="one of BASELINE.json's other configurations, counted from 1 (1 scan only, 2 256 frames, "
                          "3 2 048 frames + TransV + pdrop, 5 Qwen2.5 + dual encoder + fp8 attention), or `decode` (one "
@@ -693,6 +721,8 @@ def parse_args(argv=None):
 
 def main():
     args = parse_args()
+    if args.dump_outputs and args.config in ("decode", "1", "5"):
+        sys.exit("bench.py: --dump-outputs covers the forward runs (--config 0, 2, 3, 4)")
     if args.config == "decode":
         return config_decode(args)
     try:
@@ -766,18 +796,24 @@ def run(args, env):
             torch.distributed.barrier()
         env.sync()
 
-    with torch.inference_mode(), env.kernels(), OpTimers(K, env.event, vlm) as st:
+    # the per-operator event timers (--full) are entered after env.kernels(): they wrap what is current in K then
+    st = OpTimers(K, env.event, vlm) if args.full else None
+    with torch.inference_mode(), env.kernels(), (st if st is not None else contextlib.nullcontext()):
         for _ in range(args.warmup):
             step()
         barrier()
-        st.on = True
+        if st is not None:
+            st.on = True
         t0 = time.perf_counter()
         for _ in range(args.steps):
             out = step()
         barrier()
         dt_s = time.perf_counter() - t0
-        st.on = False
+        if st is not None:
+            st.on = False
     assert torch.isfinite(out.float()).all(), "non-finite logits"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": out})
     if os.environ.get("TV_BENCH_DRYRUN_FAIL_RANK") == str(rank):          # tests: a rank that dies must fail the job
         raise RuntimeError("TV_BENCH_DRYRUN_FAIL_RANK: this rank fails on purpose")
     t = torch.tensor([dt_s], device=dev, dtype=torch.float64)
@@ -798,20 +834,22 @@ def run(args, env):
                        "frames": T, "tokens": L, "pdrop": pd, "merge_module": "CrossAttention" if pd else "no_merge",
                        "parallelism": "single GPU" if world == 1 else f"sequence-sharded x{world} (RCCL)",
                        "weights": "random init, seed 0"},
-            # the kernel north_star names (dominant among the hand-written HBM-bound ones) ...
-            "roofline": st.scan_roofline(scan_bytes_per_token(cfg)),
-            # ... and every kernel with a stated roof, all event-timed inside the timed steps
-            "rooflines": st.all_rooflines(scan_bytes_per_token(cfg), cfg),
         }
-        # how much of the step the event-timed operators (hand-written kernels and library GEMMs) account for
-        line["timed_ms_per_step"] = round(st.accounted_ms() / args.steps, 2)
-        line["timed_share_of_step"] = round(st.accounted_ms() / args.steps / ms, 4)
-        if world == 1 and dev.type == "cuda" and line["roofline"]:
-            # What a plain copy of the same size reaches on THIS box (read + write streams, outside the timed region): the
-            # practical ceiling of an operator that reads x and writes y once — `peak` stays the 8 TB/s of the data sheet.
-            line["roofline"].update(copy_rate(dev, line["roofline"]))
-        if world == 1 and not args.no_cpu_baseline and dev.type == "cuda":
-            line["cpu_baseline"] = cpu_baseline(cfg)
+        if st is not None:
+            # the kernel north_star names (dominant among the hand-written HBM-bound ones) ...
+            line["roofline"] = st.scan_roofline(scan_bytes_per_token(cfg))
+            # ... and every kernel with a stated roof, all event-timed inside the timed steps
+            line["rooflines"] = st.all_rooflines(scan_bytes_per_token(cfg), cfg)
+            # how much of the step the event-timed operators (hand-written kernels and library GEMMs) account for
+            line["timed_ms_per_step"] = round(st.accounted_ms() / args.steps, 2)
+            line["timed_share_of_step"] = round(st.accounted_ms() / args.steps / ms, 4)
+            if world == 1 and dev.type == "cuda" and line["roofline"]:
+                # What a plain copy of the same size reaches on THIS box (read + write streams, outside the timed region):
+                # the practical ceiling of an operator that reads x and writes y once — `peak` stays the 8 TB/s of the data
+                # sheet.
+                line["roofline"].update(copy_rate(dev, line["roofline"]))
+            if world == 1 and not args.no_cpu_baseline and dev.type == "cuda":
+                line["cpu_baseline"] = cpu_baseline(cfg)
     # RCCL writes a version banner through C stdio, which is block-buffered on a pipe and would
     # otherwise surface at process exit, AFTER the result: every rank drains it before the last
     # barrier, so that rank 0's JSON line is the last line of the job's stdout

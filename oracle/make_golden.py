@@ -76,8 +76,26 @@ def npz(name, **arrs):
         if isinstance(v, torch.Tensor):
             v = v.detach().cpu().numpy()
         out[k] = np.asarray(v)
-    np.savez_compressed(OUT / f"{name}.npz", **out)
-    print(f"wrote {name}.npz  ({sum(a.nbytes for a in out.values()) / 1024:.0f} KiB raw)")
+    for i, part in enumerate(npz_parts(out)):
+        fname = f"{name}.npz" if i == 0 else f"{name}.part{i + 1}.npz"
+        np.savez_compressed(OUT / fname, **part)
+        print(f"wrote {fname}  ({sum(a.nbytes for a in part.values()) / 1024:.0f} KiB raw)")
+
+
+PART_BYTES = 960 * 1024     # a committed file stays under 1 MiB: larger fixtures go to <name>.npz, <name>.part2.npz, ...
+
+
+def npz_parts(arrs):
+    """Split {key: array} into dicts of at most PART_BYTES raw bytes each (an array larger than that goes alone),
+    in key order; tests/conftest.py:load_golden merges the parts again."""
+    parts, cur, size = [], {}, 0
+    for k, a in arrs.items():
+        if cur and size + a.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = a
+        size += a.nbytes
+    return parts + [cur]
 
 
 def sd_arrays(module, prefix="w."):

@@ -30,8 +30,13 @@ def pytest_collection_modifyitems(config, items):
 
 
 def load_golden(name):
-    z = np.load(GOLDEN / f"{name}.npz")
-    return {k: z[k] for k in z.files}
+    # a fixture larger than a committed file may be is stored in parts: <name>.npz, <name>.part2.npz, ...
+    # (oracle/make_golden.py:npz_parts)
+    out = {}
+    for path in [GOLDEN / f"{name}.npz", *sorted(GOLDEN.glob(f"{name}.part*.npz"))]:
+        z = np.load(path)
+        out.update({k: z[k] for k in z.files})
+    return out
 
 
 def golden_state_dict(g, prefix="w."):

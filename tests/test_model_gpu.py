@@ -831,3 +831,28 @@ def test_generate_with_graphed_decode_step_continues_like_the_eager_loop(monkeyp
     assert replays == []
     assert graphed.shape == eager.shape == (1, 12)
     assert torch.equal(graphed, eager), (graphed.tolist(), eager.tolist())
+
+
+@pytest.mark.parametrize("role,k", [("proj", 1152), ("fc2", 4352)])
+def test_vit_residual_accumulate_repeats_bit_for_bit(role, k):
+    """SigLIP-so400m's output projections accumulate into the residual stream (model/vit/siglip.py:_accumulate): at
+    the forward's row counts the default path must give the same bits on every call of the same inputs, within bf16
+    round-off of x + h W^T in fp32."""
+    from timeviper_amd.model.vit import siglip
+    assert role in siglip._OWN_ACCUM
+    g = torch.Generator(device=DEV).manual_seed(0)
+    M = 256 * 729
+    x0 = torch.randn(M, 1152, device=DEV, generator=g).bfloat16()
+    h = torch.randn(M, k, device=DEV, generator=g).bfloat16()
+    w = (torch.randn(1152, k, device=DEV, generator=g) * 0.02).bfloat16()
+    with torch.inference_mode():
+        first = None
+        for _ in range(40):
+            x = x0.clone()
+            siglip._accumulate(x, h, w, role)
+            if first is None:
+                first = x
+            else:
+                assert torch.equal(x, first)
+        ref = torch.addmm(x0.float(), h.float(), w.float().t())
+    assert relerr(first, ref) < 1e-2

@@ -8,7 +8,7 @@
 # prints per run: the settings, frames/s, and frac / avg launch us of the first roofline whose kernel label holds the substring
 pat=$1; shift
 for setting in "$@"; do
-  env $setting python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+  env $setting python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = [r for r in [d['roofline']] + d.get('rooflines', []) if '$pat' in r['kernel']]

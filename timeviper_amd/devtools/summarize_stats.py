@@ -10,7 +10,7 @@ line = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 title = sys.argv[3] if len(sys.argv) > 3 else "bench under rocprofv3"
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 print(f"# {title}\n")
-print("Command (on the GPU box): `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1`\n")
+print("Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 --warmup 1`\n")
 print(f"Bench line of that run: **{line['value']} frames/s**, {line['ms_per_step']} ms/step (profiler attached).\n")
 print(f"GPU time in kernels over warm-up + {line['steps']} steps: {tot / 1e9:.2f} s.\n")
 print("| kernel | calls | avg µs | max µs | % of GPU time |\n|---|---:|---:|---:|---:|")

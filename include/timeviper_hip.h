@@ -267,6 +267,26 @@ int tv_selective_state_update(void* state, const void* x, const void* dt,
                               int dstate, int dtype, int dt_softplus,
                               void* stream);
 
+/* The same step over `seqlen` = T >= 1 tokens of ONE launch: the continuation of a prefilled cache with several
+ * tokens (a follow-up question, a tool result, a draft to verify).  state (B,H,P,N) fp32, updated in place: every
+ * row is read once, kept in registers over the T tokens and written once.  x, y (B,T,H,P) with dense H*P rows,
+ * dt (B,T,H), Bm / Cm (B,T,G,N) by batch / token / group strides in elements (token-major rows or the group-major
+ * views tv_causal_conv1d_xbc_fwd writes; contiguous N).  Per token the arithmetic and rounding points of
+ * tv_selective_state_update (T == 1 gives its bits), plus the prefill scan's clamp of dt to [dt_min, dt_max] and its
+ * group_map (0: h / (H/G), 1: h % G).  d_state 16 / 32 / 64 / 128 / 256 with B / C strides that are multiples of 4
+ * elements: lanes share a row; anything else: a thread per row. */
+int tv_selective_state_update_seq(void* state, const void* x, const void* dt, const void* A,
+                                  const void* Bm, const void* Cm, const void* D, const void* dt_bias,
+                                  void* y, int batch, int seqlen, int nheads, int headdim, int ngroups,
+                                  int dstate, int64_t x_stride_b, int64_t x_stride_l, int64_t dt_stride_b,
+                                  int64_t dt_stride_l, int64_t b_stride_b, int64_t b_stride_l,
+                                  int64_t b_stride_g, int64_t c_stride_b, int64_t c_stride_l,
+                                  int64_t c_stride_g, int64_t y_stride_b, int64_t y_stride_l, int dtype,
+                                  int dt_softplus, float dt_min, float dt_max, int group_map, void* stream);
+/* which kernel the most recent tv_selective_state_update_seq of this process ran on: 1 lanes share a row, 2 a thread
+ * per row (other d_state, or B / C not aligned for the vector loads); 0 before the first call */
+int tv_selective_state_update_seq_last_impl(void);
+
 /* ------------------------------------------------------------------------
  * ViT linears with fused epilogues: C = epilogue(A . W^T), A (M,K), W (N,K) =
  * nn.Linear.weight as stored, C (M,N), all bf16 row-major with element row strides lda / ldw / ldc.
@@ -394,6 +414,24 @@ int tv_attn_decode_fwd(const void* q, const void* k, const void* v, void* o, voi
                        int64_t v_stride_l, int64_t v_stride_h, int64_t o_stride_b,
                        int64_t o_stride_h, float softmax_scale, int dtype,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same split-KV walk for a CONTINUATION: the queries are the last seqlen_q = T tokens of the seqlen_k keys
+ * (q, o (B, T, Hq, D) by batch / token / head strides; k / v already hold the T new rows).  The 16 MFMA columns hold
+ * (token c / gq, head c % gq) of a kv-head, in blocks of 16; query token i sees the keys < Lk - T + 1 + i (bottom-right
+ * causal, the mask of tv_flash_attn_fwd for seqlen_q < seqlen_k).  lse (B, Hq, T) fp32 or NULL.  seqlens_k as in
+ * tv_attn_decode_fwd (the keys in use INCLUDING the T new ones).  Supported: headdim 128, bf16, T <= 64 and
+ * T * (Hq / Hkv) <= 128 columns; anything else returns TV_ERR_UNSUPPORTED (callers: tv_flash_attn_fwd, causal).
+ * workspace: tv_attn_append_workspace_bytes(), 16-byte aligned. */
+size_t tv_attn_append_workspace_bytes(int batch, int seqlen_q, int nheads_q, int nheads_kv, int seqlen_k);
+int tv_attn_append_fwd(const void* q, const void* k, const void* v, void* o, void* lse, int batch,
+                       int seqlen_q, int seqlen_k, const int* seqlens_k, int nheads_q, int nheads_kv,
+                       int headdim, int64_t q_stride_b, int64_t q_stride_l, int64_t q_stride_h,
+                       int64_t k_stride_b, int64_t k_stride_l, int64_t k_stride_h, int64_t v_stride_b,
+                       int64_t v_stride_l, int64_t v_stride_h, int64_t o_stride_b, int64_t o_stride_l,
+                       int64_t o_stride_h, float softmax_scale, int dtype, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* launches of tv_attn_append_fwd by this process so far (tests: a call did not fall back) */
+int tv_attn_append_calls(void);
 
 /* ------------------------------------------------------------------------
  * T2  pdrop "attn" ranking.  Replaces modeling_nano.py:1822-1857,:1914-1939

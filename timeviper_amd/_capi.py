@@ -42,6 +42,11 @@ SIGNATURES = {
     "tv_ssd_scan_last_impl": (_i, []),
     "tv_ssd_head_set_asm": (None, [_i]),
     "tv_selective_state_update": (_i, [_p] * 9 + [_i] * 7 + [_p]),
+    "tv_selective_state_update_seq": (_i, [_p] * 9 + [_i] * 6 + [_l] * 12 + [_i, _i, _f, _f, _i, _p]),
+    "tv_selective_state_update_seq_last_impl": (_i, []),
+    "tv_attn_append_workspace_bytes": (_z, [_i] * 5),
+    "tv_attn_append_fwd": (_i, [_p] * 5 + [_i, _i, _i, _p, _i, _i, _i] + [_l] * 12 + [_f, _i, _p, _z, _p]),
+    "tv_attn_append_calls": (_i, []),
     "tv_gemm_bf16_fwd": (_i, [_p, _p, _p, _p, _l, _i, _i, _l, _l, _l, _i, _i, _p]),
     "tv_gemm_set_persist": (None, [_i, _i]),
     "tv_gemm_set_drip": (None, [_i]),
@@ -74,7 +79,7 @@ class TimeViperHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 12      # tv_abi_version() of the library these SIGNATURES describe (csrc/capi.cpp)
+ABI_VERSION = 13     # tv_abi_version() of the library these SIGNATURES describe (csrc/capi.cpp)
 
 
 def lib_path() -> Path:

@@ -244,6 +244,129 @@ __global__ __launch_bounds__(256) void state_update_chain_kernel(float* __restri
   }
 }
 
+// ---------------------------------------------------------------- continuation: T tokens against a resident state
+// The token recurrence of state_update_chain_kernel over T tokens of one launch (a continuation of a prefilled cache:
+// a follow-up question, a tool result, a draft to verify).  Same lane layout (LPR lanes share a row, 16 bytes each) and,
+// per token, the same arithmetic at the same rounding points — but the row is loaded once, stays in the lanes' registers
+// over the T tokens and is stored once: 2 x 5.2 MB a Nano layer whatever T is, against T x that for T launches.  What
+// streams per token is small (dt and x of the row, the lane's 4 entries of B and C: the rows of a head group read the
+// same B / C lines out of L2) and is requested SQ_PF tokens ahead of its use, a batch of tokens at a time.
+struct SeqArgs {
+  float* state;
+  const void *x, *dt, *Bm, *Cm;
+  const float *A, *D, *dt_bias;
+  void* y;
+  int T, H, P, G, N;
+  int64_t xsb, xsl, dsb, dsl, bsb, bsl, bsg, csb, csl, csg, ysb, ysl;
+  int softplus, group_map, rows_total;
+  float dt_min, dt_max;
+};
+
+constexpr int SQ_PF = 4;      // tokens whose operands are in flight while the previous SQ_PF are computed
+
+template <typename T, int LPR>
+__global__ __launch_bounds__(256) void state_update_seq_kernel(SeqArgs a) {
+  constexpr int N = 4 * LPR, RPW = 64 / LPR, WAVES = 4;
+  typedef typename std::conditional<std::is_same<T, float>::value, f32x4, typename std::conditional<std::is_same<T, bf16_t>::value, bf16x4, f16x4>::type>::type vec4_t;
+  const int lane = threadIdx.x & 63;
+  const int w = (int)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  const int sub = lane / LPR, ln = lane % LPR;
+  const int row = w * RPW + sub;                        // (b, h, p) flattened
+  const bool ok = row < a.rows_total;
+  const int rc = ok ? row : a.rows_total - 1;
+  const int bh = (int)((unsigned)rc / (unsigned)a.P);
+  const int p = rc - bh * a.P;
+  const int b = (int)((unsigned)bh / (unsigned)a.H);
+  const int h = bh - b * a.H;
+  const int g = a.group_map ? (h % a.G) : (int)((unsigned)h / (unsigned)(a.H / a.G));
+  f32x4 sv = __builtin_nontemporal_load((const f32x4*)(a.state + (int64_t)rc * N) + ln);
+  const float av = a.A[h];
+  const float bv = a.dt_bias ? a.dt_bias[h] : 0.f;
+  const float dv = a.D ? a.D[h] : 0.f;
+  const T* xp = (const T*)a.x + (int64_t)b * a.xsb + (int64_t)h * a.P + p;
+  const T* dp = (const T*)a.dt + (int64_t)b * a.dsb + h;
+  const T* Bp = (const T*)a.Bm + (int64_t)b * a.bsb + (int64_t)g * a.bsg + 4 * ln;
+  const T* Cp = (const T*)a.Cm + (int64_t)b * a.csb + (int64_t)g * a.csg + 4 * ln;
+  T* yp = (T*)a.y + (int64_t)b * a.ysb + (int64_t)h * a.P + p;
+
+  T dtc[SQ_PF], xc[SQ_PF], dtn[SQ_PF], xn[SQ_PF];
+  vec4_t Bc[SQ_PF], Cc[SQ_PF], Bn[SQ_PF], Cn[SQ_PF];
+#pragma unroll
+  for (int j = 0; j < SQ_PF; ++j) {
+    const int64_t t = min(j, a.T - 1);                  // (past the end: the last token again, never used)
+    dtc[j] = dp[t * a.dsl];
+    xc[j] = xp[t * a.xsl];
+    Bc[j] = *(const vec4_t*)(Bp + t * a.bsl);
+    Cc[j] = *(const vec4_t*)(Cp + t * a.csl);
+  }
+  for (int t0 = 0; t0 < a.T; t0 += SQ_PF) {
+#pragma unroll
+    for (int j = 0; j < SQ_PF; ++j) {
+      const int64_t t = min(t0 + SQ_PF + j, a.T - 1);
+      dtn[j] = dp[t * a.dsl];
+      xn[j] = xp[t * a.xsl];
+      Bn[j] = *(const vec4_t*)(Bp + t * a.bsl);
+      Cn[j] = *(const vec4_t*)(Cp + t * a.csl);
+    }
+#pragma unroll
+    for (int j = 0; j < SQ_PF; ++j) {
+      if (t0 + j < a.T) {                               // wave-uniform
+        float d = to_f32(dtc[j]) + bv;
+        if (a.softplus) d = softplus_f(d);
+        d = fminf(fmaxf(d, a.dt_min), a.dt_max);
+        const float dec = expf(d * av);
+        const float xr = to_f32(xc[j]);
+        const float xv = d * xr;
+        float part = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          sv[i] = fmaf(dec, sv[i], xv * to_f32(Bc[j][i]));
+          part = fmaf(sv[i], to_f32(Cc[j][i]), part);
+        }
+        part = group_sum_dpp<LPR>(part);
+        if (ok && ln == LPR - 1) yp[(int64_t)(t0 + j) * a.ysl] = from_f32<T>(fmaf(dv, xr, part));
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SQ_PF; ++j) {
+      dtc[j] = dtn[j];
+      xc[j] = xn[j];
+      Bc[j] = Bn[j];
+      Cc[j] = Cn[j];
+    }
+  }
+  if (ok) __builtin_nontemporal_store(sv, (f32x4*)(a.state + (int64_t)row * N) + ln);
+}
+
+// any d_state: a thread per row, the row walked in memory once per token (it stays in the thread's cache lines)
+template <typename T>
+__global__ void state_update_seq_rows_kernel(SeqArgs a) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const int h = blockIdx.y, b = blockIdx.z;
+  if (p >= a.P) return;
+  const int N = a.N;
+  const int g = a.group_map ? (h % a.G) : h / (a.H / a.G);
+  const float Ah = a.A[h], bias = a.dt_bias ? a.dt_bias[h] : 0.f, Dh = a.D ? a.D[h] : 0.f;
+  float* s = a.state + (((int64_t)b * a.H + h) * a.P + p) * N;
+  for (int t = 0; t < a.T; ++t) {
+    float d = to_f32(((const T*)a.dt)[(int64_t)b * a.dsb + (int64_t)t * a.dsl + h]) + bias;
+    if (a.softplus) d = softplus_f(d);
+    d = fminf(fmaxf(d, a.dt_min), a.dt_max);
+    const float dec = expf(d * Ah);
+    const float xr = to_f32(((const T*)a.x)[(int64_t)b * a.xsb + (int64_t)t * a.xsl + (int64_t)h * a.P + p]);
+    const float xv = d * xr;
+    const T* Br = (const T*)a.Bm + (int64_t)b * a.bsb + (int64_t)t * a.bsl + (int64_t)g * a.bsg;
+    const T* Cr = (const T*)a.Cm + (int64_t)b * a.csb + (int64_t)t * a.csl + (int64_t)g * a.csg;
+    float acc = 0.f;
+    for (int n = 0; n < N; ++n) {
+      const float v = fmaf(dec, s[n], xv * to_f32(Br[n]));
+      s[n] = v;
+      acc = fmaf(v, to_f32(Cr[n]), acc);
+    }
+    ((T*)a.y)[(int64_t)b * a.ysb + (int64_t)t * a.ysl + (int64_t)h * a.P + p] = from_f32<T>(fmaf(Dh, xr, acc));
+  }
+}
+
 }  // namespace
 
 // called from ssd_scan.hip (dispatcher)
@@ -318,5 +441,64 @@ extern "C" int tv_selective_state_update(void* state, const void* x, const void*
     default: TV_UNSUPPORTED("selective_state_update: dtype %d", dtype);
   }
 #undef TV_SU
+  TV_LAUNCH_CHECK();
+}
+
+static int g_seq_last_impl = 0;
+extern "C" int tv_selective_state_update_seq_last_impl(void) { return g_seq_last_impl; }
+
+extern "C" int tv_selective_state_update_seq(void* state, const void* x, const void* dt, const void* A,
+                                             const void* Bm, const void* Cm, const void* D, const void* dt_bias,
+                                             void* y, int batch, int seqlen, int nheads, int headdim, int ngroups,
+                                             int dstate, int64_t xsb, int64_t xsl, int64_t dsb, int64_t dsl,
+                                             int64_t bsb, int64_t bsl, int64_t bsg, int64_t csb, int64_t csl,
+                                             int64_t csg, int64_t ysb, int64_t ysl, int dtype, int dt_softplus,
+                                             float dt_min, float dt_max, int group_map, void* stream) {
+  TV_CHECK_ARG(state && x && dt && A && Bm && Cm && y, "selective_state_update_seq: null pointer");
+  TV_CHECK_ARG(batch > 0 && seqlen > 0 && nheads > 0 && headdim > 0 && ngroups > 0 && dstate > 0 &&
+                   nheads % ngroups == 0,
+               "selective_state_update_seq: bad sizes");
+  TV_CHECK_ARG(xsl >= (int64_t)nheads * headdim && ysl >= (int64_t)nheads * headdim && dsl >= nheads,
+               "selective_state_update_seq: x / y / dt rows overlap");
+  if (dtype != TV_F32 && dtype != TV_BF16 && dtype != TV_F16) TV_UNSUPPORTED("selective_state_update_seq: dtype %d", dtype);
+  hipStream_t s = (hipStream_t)stream;
+  SeqArgs a;
+  a.state = (float*)state; a.x = x; a.dt = dt; a.Bm = Bm; a.Cm = Cm;
+  a.A = (const float*)A; a.D = (const float*)D; a.dt_bias = (const float*)dt_bias; a.y = y;
+  a.T = seqlen; a.H = nheads; a.P = headdim; a.G = ngroups; a.N = dstate;
+  a.xsb = xsb; a.xsl = xsl; a.dsb = dsb; a.dsl = dsl; a.bsb = bsb; a.bsl = bsl; a.bsg = bsg;
+  a.csb = csb; a.csl = csl; a.csg = csg; a.ysb = ysb; a.ysl = ysl;
+  a.softplus = dt_softplus; a.group_map = group_map; a.dt_min = dt_min; a.dt_max = dt_max;
+  const int64_t rows = (int64_t)batch * nheads * headdim;
+  a.rows_total = (int)(rows < (1ll << 31) ? rows : 0);
+  // the lanes of a row read 4 entries of B / C as one vector: 16-byte aligned pieces for fp32, 8-byte for the 16-bit types
+  const int lpr = dstate / 4;
+  const int64_t bc = bsb | bsl | bsg | csb | csl | csg;
+  const uintptr_t bc_align = dtype == TV_F32 ? 15 : 7;
+  if (dstate % 4 == 0 && (lpr == 4 || lpr == 8 || lpr == 16 || lpr == 32 || lpr == 64) && (((uintptr_t)state) & 15) == 0 &&
+      (((uintptr_t)Bm | (uintptr_t)Cm) & bc_align) == 0 && bc % 4 == 0 && rows < (1ll << 31)) {
+    g_seq_last_impl = 1;
+    const int64_t rows_per_block = 4 * (64 / lpr);
+    const dim3 rgrid((unsigned)((rows + rows_per_block - 1) / rows_per_block));
+#define TV_SQ(T, LPR) state_update_seq_kernel<T, LPR><<<rgrid, 256, 0, s>>>(a)
+#define TV_SQ_T(T)                                                                                          \
+    switch (lpr) { case 4: TV_SQ(T, 4); break; case 8: TV_SQ(T, 8); break; case 16: TV_SQ(T, 16); break;       \
+                   case 32: TV_SQ(T, 32); break; default: TV_SQ(T, 64); break; }
+    switch (dtype) {
+      case TV_F32: TV_SQ_T(float); break;
+      case TV_BF16: TV_SQ_T(bf16_t); break;
+      default: TV_SQ_T(f16_t); break;
+    }
+#undef TV_SQ_T
+#undef TV_SQ
+    TV_LAUNCH_CHECK();
+  }
+  g_seq_last_impl = 2;
+  dim3 grid((headdim + 63) / 64, nheads, batch);
+  switch (dtype) {
+    case TV_F32: state_update_seq_rows_kernel<float><<<grid, 64, 0, s>>>(a); break;
+    case TV_BF16: state_update_seq_rows_kernel<bf16_t><<<grid, 64, 0, s>>>(a); break;
+    default: state_update_seq_rows_kernel<f16_t><<<grid, 64, 0, s>>>(a); break;
+  }
   TV_LAUNCH_CHECK();
 }

@@ -449,6 +449,50 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None,
     return y
 
 
+def selective_state_update_seq(state, x, dt, A, B, C, D=None, dt_bias=None, dt_softplus=False,
+                               dt_limit=(0.0, float("inf")), group_map="block", out=None):
+    """T tokens against a resident state — the continuation of a prefilled cache (tv_selective_state_update_seq).
+    state (B,H,P,N) fp32, in place; x (B,T,H,P), dt (B,T,H), B / C (B,T,G,N) (token-major or the group-major views of
+    `causal_conv1d_xbc`, no copy), A / D / dt_bias (H).  Returns y (B,T,H,P) (`out`, when given).  Per token the arithmetic of
+    `selective_state_update` with the prefill scan's dt clamp and group map."""
+    _gpu(state, x, dt, A, B, C, D, dt_bias)
+    Bsz, T, H, P = x.shape
+    G, N = B.shape[2], B.shape[3]
+    if state.dtype != torch.float32 or not state.is_contiguous() or state.shape != (Bsz, H, P, N):
+        raise TimeViperHipError("selective_state_update_seq: state must be contiguous fp32 (B, H, P, N)")
+    if T < 1:
+        raise TimeViperHipError("selective_state_update_seq: at least one token")
+    if dt.dtype != x.dtype:
+        dt = dt.to(x.dtype)
+    if B.dtype != x.dtype:
+        B = B.to(x.dtype)
+    if C.dtype != x.dtype:
+        C = C.to(x.dtype)
+    x, xsb, xsl = _row_view(x, H * P)
+    dt, dsb, dsl = _row_view(dt, H)
+    if B.stride(3) != 1:
+        B = B.contiguous()
+    if C.stride(3) != 1:
+        C = C.contiguous()
+    f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()
+    A, D, dt_bias = f32(A), f32(D), f32(dt_bias)
+    y = torch.empty((Bsz, T, H, P), dtype=x.dtype, device=x.device) if out is None else out
+    if y.shape != (Bsz, T, H, P) or y.dtype != x.dtype or y.stride(3) != 1 or y.stride(2) != P or not y.is_cuda:
+        raise TimeViperHipError("selective_state_update_seq: out must be (B, T, H, P) of x's dtype with dense H * P rows")
+    check(_capi.lib().tv_selective_state_update_seq(
+        _p(state), _p(x), _p(dt), _p(A), _p(B), _p(C), _p(D), _p(dt_bias), _p(y), Bsz, T, H, P, G, N,
+        xsb, xsl, dsb, dsl, B.stride(0), B.stride(1), B.stride(2), C.stride(0), C.stride(1), C.stride(2),
+        y.stride(0), y.stride(1), _dt(x), int(bool(dt_softplus)), float(dt_limit[0]),
+        float(min(dt_limit[1], 3.0e38)), {"block": 0, "tile": 1}[group_map], _stream()),
+        "tv_selective_state_update_seq")
+    return y
+
+
+def selective_state_update_seq_last_impl() -> int:
+    """1: the most recent `selective_state_update_seq` ran with lanes sharing a state row, 2: a thread per row."""
+    return int(_capi.lib().tv_selective_state_update_seq_last_impl())
+
+
 def ssd_scan_set_impl(impl: int) -> None:
     """0 auto (= 6 where it applies, else 4, 3; other dtypes / d_state: 8, else 1), 1 generic fp32 token recurrence, 3 MFMA
     slice march on <= 40-column slices of a head, 4 whole-head slice march x sequence segments, 6 head-per-wave march
@@ -884,3 +928,46 @@ def patch_embed_video(pixels, weight, bias=None, pos=None):
         _p(pixels), _p(w), _p(b), _p(ps), _p(out), B * T, Cin, H, W, p, Dout, T,
         Cin * T * H * W, H * W, T * H * W, _dt(pixels), _p(ws), _stream()), "tv_patch_embed_strided_fwd")
     return out
+
+
+def flash_attn_append_calls() -> int:
+    """Launches of tv_attn_append_fwd by this process (tests: a continuation's attention did not fall back)."""
+    return int(_capi.lib().tv_attn_append_calls())
+
+
+def flash_attn_append(q, k, v, seqlens_k=None, softmax_scale=None, return_lse=False):
+    """Attention of a continuation: q (B, T, Hq, 128) bf16 are the LAST T tokens of the Lk keys in k / v (B, Lk, Hkv, 128)
+    (the cache with the T new rows appended); query token i sees the keys < Lk - T + 1 + i.  Split-KV over the chip like
+    `flash_attn_decode`, the T x (Hq / Hkv) columns of a kv-head sharing one pass over its K / V.  `seqlens_k`: int32 (B,)
+    on the GPU, the keys in use (None: Lk).  Shapes the kernel does not take (T > 64, T * Hq / Hkv > 128, other head dims /
+    dtypes) run on `flash_attn_func(causal=True)`, which has the same bottom-right mask."""
+    _gpu(q, k, v, seqlens_k)
+    B, T, Hq, D = q.shape
+    Lk, Hkv = k.shape[1], k.shape[2]
+    if seqlens_k is not None and (seqlens_k.dtype != torch.int32 or seqlens_k.numel() != B or not seqlens_k.is_contiguous()):
+        raise TimeViperHipError("flash_attn_append: seqlens_k must be a contiguous int32 tensor of `batch` entries")
+    fix = lambda t: t if t.stride(-1) == 1 else t.contiguous()
+    q, k, v = fix(q), fix(k), fix(v)
+    takes = (q.dtype == torch.bfloat16 and D == 128 and 1 <= T <= 64 and T * (Hq // Hkv) <= 128 and Lk >= T
+             and all(s % 8 == 0 for t in (q, k, v) for s in t.stride()[:3])
+             and all(t.data_ptr() % 16 == 0 for t in (q, k, v)))
+    if not takes:
+        if seqlens_k is not None:
+            raise TimeViperHipError("flash_attn_append: seqlens_k needs the split-KV kernel (bf16, head_dim 128, T <= 64, "
+                                    "T * Hq / Hkv <= 128)")
+        return flash_attn_func(q, k, v, softmax_scale=softmax_scale, causal=True, return_lse=return_lse)
+    scale = 1.0 / math.sqrt(D) if softmax_scale is None else float(softmax_scale)
+    o = torch.empty((B, T, Hq, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, Hq, T), dtype=torch.float32, device=q.device) if return_lse else None
+    lib = _capi.lib()
+    ws = torch.empty((max(int(lib.tv_attn_append_workspace_bytes(B, T, Hq, Hkv, Lk)), 16),), dtype=torch.uint8,
+                     device=q.device)
+    st = lib.tv_attn_append_fwd(
+        _p(q), _p(k), _p(v), _p(o), _p(lse), B, T, Lk, _p(seqlens_k), Hq, Hkv, D,
+        q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
+        v.stride(0), v.stride(1), v.stride(2), o.stride(0), o.stride(1), o.stride(2),
+        scale, _dt(q), _p(ws), ws.numel(), _stream())
+    if st == -2 and seqlens_k is None:      # TV_ERR_UNSUPPORTED (e.g. a row stride too large for a split)
+        return flash_attn_func(q, k, v, softmax_scale=softmax_scale, causal=True, return_lse=return_lse)
+    check(st, "tv_attn_append_fwd")
+    return (o, lse) if return_lse else o

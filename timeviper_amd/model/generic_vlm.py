@@ -219,7 +219,11 @@ class GenericTimeViperVLM(nn.Module):
                 visual_embeddings: Optional[torch.Tensor] = None) -> CausalLMOutputWithPast:
         if self.training:
             raise NotImplementedError("timeviper_amd implements the inference forward only")
-        if pixel_values is None and pixel_values_videos is None and visual_embeddings is None:
+        has_pixels = not (pixel_values is None and pixel_values_videos is None and visual_embeddings is None)
+        if has_pixels and past_key_values is not None and cache_position is not None and int(cache_position[0]) > 0:
+            raise NotImplementedError("a continuation (cache_position > 0) takes text only: new frames behind the "
+                                      "token-drop stages of a finished prefill are not implemented")
+        if not has_pixels:
             return self.llm_backbone(input_ids=input_ids, attention_mask=None,
                                      position_ids=position_ids, past_key_values=past_key_values,
                                      inputs_embeds=inputs_embeds, use_cache=use_cache,
@@ -282,7 +286,11 @@ class GenericTimeViperVLM(nn.Module):
         the reference's return contract (generic_vlm.py:743-760): the DECODED text of the new tokens
         (prompt stripped, `.strip()`-ed), which evaluate.py:529 hands to `extract_answer`.
         `return_ids=True` (or HF's `return_dict_in_generate=True`, or a tokenizer without `decode`)
-        returns the (1, n_new) id tensor instead."""
+        returns the (1, n_new) id tensor instead.
+        Conversations: `return_past_key_values=True` returns `(result, cache)`; the cache records in `pending_ids` the
+        ids emitted but not yet run through the model.  `past_key_values=cache` with the next turn's `input_ids` (text
+        only) feeds pending ids + new ids + `answer_prompt` through ONE continuation forward of that cache instead of
+        a new prefill, then decodes as usual."""
         input_ids = args[0] if args else kwargs.pop("input_ids", None)
         pixel_values = kwargs.pop("pixel_values", None)
         pixel_values_videos = kwargs.pop("pixel_values_videos", None)
@@ -295,22 +303,51 @@ class GenericTimeViperVLM(nn.Module):
         eos = self.eos_token_ids_to_use if eos is None else eos
         eos = set(int(t) for t in (eos if isinstance(eos, (list, tuple)) else [eos]))
         llm = self.llm_backbone.llm
-        cache = llm.new_cache(1, dtype=self.dtype, device=self.device)
+        cache = kwargs.pop("past_key_values", None)
+        return_cache = bool(kwargs.pop("return_past_key_values", False))
         mi = self.prepare_inputs_for_generation(input_ids, past_key_values=None, attention_mask=attention_mask,
                                                 pixel_values=pixel_values, pixel_values_videos=pixel_values_videos,
                                                 answer_prompt=kwargs.pop("answer_prompt", None))
-        out = self.forward(input_ids=mi["input_ids"], pixel_values=mi["pixel_values"],
-                           pixel_values_videos=mi["pixel_values_videos"], past_key_values=cache,
-                           use_cache=True, cache_position=mi["cache_position"])
-        new_tokens: List[int] = []
-        tok = out.logits[:, -1].argmax(-1)
         pdargs = self.pdrop_args if self.use_pdrop else None
+        if cache is None:
+            cache = llm.new_cache(1, dtype=self.dtype, device=self.device)
+            out = self.forward(input_ids=mi["input_ids"], pixel_values=mi["pixel_values"],
+                               pixel_values_videos=mi["pixel_values_videos"], past_key_values=cache,
+                               use_cache=True, cache_position=mi["cache_position"])
+            # the drop bookkeeping of THIS prefill (tokens per stage: the position shift of every later token) travels
+            # with its cache: the model object may prefill another video before the conversation goes on
+            cache.pdrop_args = dict(pdargs) if pdargs is not None else None
+        else:
+            # the next turn of a conversation: the ids the last turn emitted but never fed + this turn's ids (+ the
+            # answer prompt) go through ONE continuation forward of the cache the last turn left
+            if mi["pixel_values"] is not None or mi["pixel_values_videos"] is not None:
+                raise NotImplementedError("generate(past_key_values=...) continues with text only: new frames behind "
+                                          "the token-drop stages of a finished prefill are not implemented")
+            if hasattr(cache, "end_static_decode"):
+                cache.end_static_decode()          # the last turn's fixed buffers: rows are appended again
+            if getattr(cache, "attention_layers", None) and cache.get_seq_length() == 0:
+                raise ValueError("generate(past_key_values=...): the cache holds no prefill")
+            pdargs = getattr(cache, "pdrop_args", pdargs)
+            ids = mi["input_ids"].to(self.device)
+            pending = getattr(cache, "pending_ids", None)
+            if pending is not None and pending.numel():
+                ids = torch.cat([pending.to(ids.device).view(1, -1), ids], dim=1)
+            # the position convention of the decode step (prepare_inputs_for_generation, reference :797-826): the tokens the
+            # first attention layer holds — what T single steps would be given, so that the two stay interchangeable
+            past_len = max(cache.get_seq_length(), 1)
+            pos = (past_len + torch.arange(ids.shape[1], device=ids.device)).unsqueeze(0)
+            out = self.llm_backbone(input_ids=ids, past_key_values=cache, use_cache=True,
+                                    cache_position=torch.tensor([past_len]), position_ids=pos, train_pdrop_args=pdargs)
+        new_tokens: List[int] = []
+        fed = 0                               # how many of them went through the model
+        tok = out.logits[:, -1].argmax(-1)
         stepper = self._graphed_decode_step(cache, max_new_tokens, pdargs)
         for _ in range(max_new_tokens):
             t = int(tok)
             new_tokens.append(t)
             if t in eos:
                 break
+            fed += 1
             if stepper is not None:            # the same step as below, replayed as one hipGraph launch
                 tok = stepper.step(tok.view(1, 1))
                 continue
@@ -321,10 +358,11 @@ class GenericTimeViperVLM(nn.Module):
                                     train_pdrop_args=pdargs)
             tok = out.logits[:, -1].argmax(-1)
         ids = torch.tensor([new_tokens], device=self.device)
+        cache.pending_ids = ids[:, fed:].clone()
         tokenizer = self.llm_backbone.tokenizer
-        if return_ids or not hasattr(tokenizer, "decode"):
-            return ids
-        return tokenizer.decode(ids[0], skip_special_tokens=False).strip()
+        result = ids if return_ids or not hasattr(tokenizer, "decode") \
+            else tokenizer.decode(ids[0], skip_special_tokens=False).strip()
+        return (result, cache) if return_cache else result
 
     def _graphed_decode_step(self, cache, max_new_tokens, pdargs):
         """The decode step behind `generate` as a captured graph (llm/decode_graph.py) where the stack allows it: the

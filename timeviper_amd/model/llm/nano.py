@@ -181,6 +181,9 @@ class HybridMambaAttentionDynamicCache:
         self._kv_len = [0] * n
         # static decode: per distinct cache length an int64 (1,) write slot and an int32 (B,) key count, on the device
         self._static, self._static_of, self.static_decode = {}, {}, False
+        # ids `generate` emitted but has not run through the model yet (it stops before feeding its last token): the
+        # next turn's continuation feeds them in front of its own ids
+        self.pending_ids: Optional[torch.Tensor] = None
 
     def _reserve(self, layer_idx, need):
         have = self._kv_len[layer_idx]
@@ -270,6 +273,31 @@ class HybridMambaAttentionDynamicCache:
         k = self.key_cache[self.attention_layers[0]]
         return 0 if k.shape[-1] == 0 else k.shape[1]
 
+    def clone(self) -> "HybridMambaAttentionDynamicCache":
+        """Deep copy of the conv / SSM states and of K / V at their current lengths (spare capacity is not copied, a
+        static-decode mode is not inherited): one prefilled video forks into several questions."""
+        new = object.__new__(type(self))
+        new.__dict__.update({k: v for k, v in self.__dict__.items()
+                             if k not in ("conv_states", "ssm_states", "key_cache", "value_cache", "_kv_buf", "_kv_len",
+                                          "_static", "_static_of", "static_decode", "pending_ids", "pdrop_args")})
+        new.transformer_layers, new.attention_layers = list(self.transformer_layers), list(self.attention_layers)
+        new.conv_states = [t.clone() for t in self.conv_states]
+        new.ssm_states = [t.clone() for t in self.ssm_states]
+        new.key_cache = [t.clone() for t in self.key_cache]
+        new.value_cache = [t.clone() for t in self.value_cache]
+        n = len(self.key_cache)
+        new._kv_buf = [None] * n
+        new._kv_len = list(self._kv_len)
+        for i in range(n):
+            if self._kv_buf[i] is not None:         # a buffer of exactly the tokens held: the next append grows it
+                new._kv_buf[i] = (new.key_cache[i], new.value_cache[i])
+        new._static, new._static_of, new.static_decode = {}, {}, False
+        pending = getattr(self, "pending_ids", None)
+        new.pending_ids = None if pending is None else pending.clone()
+        if getattr(self, "pdrop_args", None) is not None:
+            new.pdrop_args = dict(self.pdrop_args)
+        return new
+
     def update_conv_state(self, layer_idx, new_conv_state, cache_init=False):
         assert cache_init
         self.conv_states[layer_idx] = new_conv_state
@@ -286,6 +314,24 @@ def _fused_decode(x: torch.Tensor) -> bool:
     the prologue; TV_DECODE_FUSED=0 keeps torch.nn.Linear + the stand-alone kernels (same arithmetic, library GEMV)."""
     return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3 and x.shape[1] == 1 and x.shape[0] <= 4
             and not torch.is_grad_enabled() and os.environ.get("TV_DECODE_FUSED", "1") != "0")
+
+
+# a continuation (T > 1 tokens behind a prefill) of up to this many tokens updates the SSM state in place, token by token
+# inside one launch; longer ones run the chunked scan from the cached state.  Measured (devtools/bench_continue.py,
+# profiles/continue_kernels.json, 9B dims): the largest T at which the sequence kernel is still the fastest of {itself,
+# T single-token launches, the scan at L = T} — 26.6 us a layer against 28.4 us for the scan at T = 16, 49.5 against 29.5 at
+# T = 32.  TV_CONTINUE_TSEQ overrides it (tests).
+CONTINUE_T_SEQ = 16
+CONTINUE_LAST_PATH = None      # "seq" / "scan": what the most recent Mamba continuation of this process ran on (tests)
+
+
+def continue_t_seq() -> int:
+    return int(os.environ.get("TV_CONTINUE_TSEQ", CONTINUE_T_SEQ))
+
+
+def is_continuation(past_key_values, cache_position) -> bool:
+    """A forward behind a finished prefill: a cache and a first position > 0 (one token: the decode step)."""
+    return past_key_values is not None and cache_position is not None and int(cache_position[0]) > 0
 
 
 def _linear(mod: nn.Linear, x: torch.Tensor) -> torch.Tensor:
@@ -384,8 +430,9 @@ class NemotronHMamba2Mixer(nn.Module):
         gate, xBC, dt = projected_states.split([d_in, self.conv_dim, self.num_heads], dim=-1)
         w = self.conv1d.weight.squeeze(1)
         negA, D32, dtb32 = self._consts()
+        if decode and seq_len > 1:
+            return self._continue(cache_params, gate, xBC, dt, w, negA, D32, dtb32)
         if decode:
-            assert seq_len == 1
             xBC = K.causal_conv1d_update(xBC[:, 0], cache_params.conv_states[self.layer_idx], w,
                                          self.conv1d.bias, self.activation)
             x, Bm, Cm = torch.split(xBC, [d_in, gts, gts], dim=-1)
@@ -425,6 +472,36 @@ class NemotronHMamba2Mixer(nn.Module):
             return out, ssm_state, res[2]
         return out
 
+    def _continue(self, cache_params, gate, xBC, dt, w, negA, D32, dtb32):
+        """T > 1 tokens behind a prefill (or earlier continuations / decode steps): the conv starts from the cached
+        pre-conv rows, the recurrence from the cached state.  Up to `continue_t_seq()` tokens the state stays where it
+        is (tv_selective_state_update_seq: every row read and written once); longer runs take the chunked scan with
+        the cached state as its initial state."""
+        global CONTINUE_LAST_PATH
+        batch_size, seq_len, _ = xBC.shape
+        d_in, Kw, idx = self.intermediate_size, self.conv_kernel_size, self.layer_idx
+        conv_state = cache_params.conv_states[idx]                       # (B, C, K): the last K pre-conv rows
+        halo = conv_state[..., 1:].transpose(1, 2)                       # (B, K-1, C)
+        new_state = torch.cat([conv_state, xBC.transpose(1, 2).to(conv_state.dtype)], dim=-1)[..., -Kw:]
+        scan = seq_len > continue_t_seq()
+        out = K.causal_conv1d_xbc(xBC, w, self.conv1d.bias, d_in, self.n_groups, self.ssm_state_size,
+                                  activation=self.activation, halo=halo, return_cb=scan)
+        conv_state.copy_(new_state)                                      # (after the conv has read the halo)
+        x, Bm, Cm = out[:3]
+        x = x.view(batch_size, seq_len, -1, self.head_dim)
+        if scan:
+            dt_limit = {} if self.time_step_limit == (0.0, float("inf")) else {"dt_limit": self.time_step_limit}
+            y, ssm_state = K.mamba_chunk_scan_combined(
+                x, dt, negA, Bm, Cm, chunk_size=self.chunk_size, D=D32, z=None, seq_idx=None,
+                return_final_states=True, dt_bias=dtb32, dt_softplus=True,
+                initial_states=cache_params.ssm_states[idx], group_map=self.group_map, cb=out[3], **dt_limit)
+            cache_params.update_ssm_state(idx, ssm_state)
+        else:
+            y = K.selective_state_update_seq(cache_params.ssm_states[idx], x, dt, negA, Bm, Cm, D=D32, dt_bias=dtb32,
+                                             dt_softplus=True, dt_limit=self.time_step_limit, group_map=self.group_map)
+        CONTINUE_LAST_PATH = "scan" if scan else "seq"
+        y = self.norm(y.reshape(batch_size, seq_len, d_in), gate)
+        return self.out_proj(y)
 
     def decode_fused(self, hidden, delta, norm, cache_params):
         """One decode token with the block's RMSNorm (+ residual add) inside in_proj and the gated norm inside out_proj:
@@ -519,6 +596,9 @@ class NemotronHAttention(nn.Module):
             # static decode: the whole buffers + the key count on the device (same launch parameters every token)
             kb, vb = past_key_value.kv_buffers(self.layer_idx)
             o = K.flash_attn_decode(q, kb, vb, seqlens_k=past_key_value.decode_lens(self.layer_idx))
+        elif q_len > 1 and is_continuation(past_key_value, cache_position):
+            # a continuation: the T new rows are in the cache, the T queries are its last T tokens (split-KV kernel)
+            o = K.flash_attn_append(q, k, v)
         else:
             o = K._flash_attention_forward(q, k, v, attention_mask=None, query_length=q_len,
                                            is_causal=self.is_causal)
@@ -743,11 +823,17 @@ class NemotronHModel(PdropMixin, nn.Module):
             cache_position = torch.arange(hidden.shape[1], device=hidden.device)
         if position_ids is None:
             position_ids = cache_position.unsqueeze(0)
+            if position_ids.shape[1] == 1 and hidden.shape[1] > 1:      # a continuation given its first position only
+                position_ids = position_ids + torch.arange(hidden.shape[1], device=position_ids.device)
         labels = kwargs.get("labels", None)
         all_hidden = () if output_hidden_states else None
         train_pdrop_args = kwargs.get("train_pdrop_args")
         self.last_pdrop_trace = []
         delta = None  # pending mixer output, added inside the next fused norm
+        continuation = is_continuation(past_key_values, cache_position)
+        if continuation and hidden.shape[1] > 1 and getattr(past_key_values, "static_decode", False):
+            raise RuntimeError("continuation: the cache is in static-decode mode (fixed buffers, one token per step); "
+                               "call cache.end_static_decode() before appending several tokens")
         fused_step = (_fused_decode(hidden) and past_key_values is not None and cache_position is not None
                       and int(cache_position[0]) > 0 and not output_hidden_states and not self.check_nan
                       and hidden.shape[-1] % 8 == 0 and hidden.shape[-1] <= 8192
@@ -759,14 +845,15 @@ class NemotronHModel(PdropMixin, nn.Module):
                     and layer_idx in self.pdrop_layers \
                     and train_pdrop_args.get("is_interleaved", False) is False:
                 stage = self.pdrop_layers.index(layer_idx)
-                if hidden.shape[1] != 1:
+                # ranking and dropping belong to the prefill: a continuation of any length carries no vision tokens
+                if hidden.shape[1] != 1 and not continuation:
                     if delta is not None:
                         hidden, delta = hidden + delta, None
                     position_ids, attention_mask, hidden, labels, _ = self.flash_rank_drop(
                         cur_num=stage, rank_layer=layer_idx, features=hidden,
                         position_ids=position_ids, attention_mask=attention_mask, labels=labels,
                         train_pdrop_args=train_pdrop_args)
-                else:  # decode: shift positions by the tokens dropped at this stage (:1666-1689)
+                else:  # decode / continuation: shift positions by the tokens dropped at this stage (:1666-1689)
                     nv = train_pdrop_args["num_vision_tokens"][0]
                     position_ids = position_ids - (int(nv * self.pdrop_ratios[stage])
                                                    - int(nv * self.pdrop_ratios[stage + 1]))

@@ -157,7 +157,10 @@ class Qwen2Attention(nn.Module):
         K.apply_rotary_pos_emb_(q, k, cos, sin)
         if past_key_values is not None:
             k, v = past_key_values.update(k, v, self.layer_idx)
-        o = K.flash_attn_func(q, k, v, softmax_scale=self.scaling, causal=True)
+        if past_key_values is not None and 1 < L < k.shape[1]:      # a continuation: the last L of the cached keys
+            o = K.flash_attn_append(q, k, v, softmax_scale=self.scaling)
+        else:
+            o = K.flash_attn_func(q, k, v, softmax_scale=self.scaling, causal=True)
         return self.o_proj(o.reshape(B, L, self.num_heads * self.head_dim)), None
 
 
@@ -286,11 +289,14 @@ class Qwen2Model(PdropMixin, nn.Module):
         if use_cache and past_key_values is None:
             past_key_values = Qwen2KVCache(self.config.num_hidden_layers)
         hidden = inputs_embeds
+        seen = past_key_values.get_seq_length() if past_key_values is not None else 0
+        continuation = seen > 0          # tokens behind a prefill: one (the decode step) or several
         if cache_position is None:
-            seen = past_key_values.get_seq_length() if past_key_values is not None else 0
             cache_position = torch.arange(seen, seen + hidden.shape[1], device=hidden.device)
         if position_ids is None:
             position_ids = cache_position.unsqueeze(0).to(hidden.device)
+            if position_ids.shape[1] == 1 and hidden.shape[1] > 1:      # a continuation given its first position only
+                position_ids = position_ids + torch.arange(hidden.shape[1], device=hidden.device)
         pos_emb = self.rotary_emb(hidden, position_ids)
         train_pdrop_args = kwargs.get("train_pdrop_args")
         self.last_pdrop_trace = []
@@ -298,7 +304,7 @@ class Qwen2Model(PdropMixin, nn.Module):
         for layer_idx, layer in enumerate(self.layers):
             if self.use_pdrop and layer_idx in self.pdrop_layers:
                 stage = self.pdrop_layers.index(layer_idx)
-                if hidden.shape[1] != 1:                       # prefill (:918-966)
+                if hidden.shape[1] != 1 and not continuation:  # prefill (:918-966)
                     if train_pdrop_args is None:
                         raise ValueError("train_pdrop_args must be provided for pdrop during prefill/training.")
                     if delta is not None:
@@ -307,7 +313,7 @@ class Qwen2Model(PdropMixin, nn.Module):
                         cur_num=stage, rank_layer=layer_idx, features=hidden, position_ids=position_ids,
                         attention_mask=attention_mask, labels=labels, train_pdrop_args=train_pdrop_args)
                     pos_emb = self.rotary_emb(hidden, position_ids)
-                else:                                          # decode: shift the position (:968-987)
+                else:                                          # decode / continuation: shift the positions (:968-987)
                     nv = train_pdrop_args["num_vision_tokens"][0]
                     position_ids = position_ids - (int(nv * self.pdrop_ratios[stage])
                                                    - int(nv * self.pdrop_ratios[stage + 1]))

@@ -131,6 +131,18 @@ def test_attention_kernels_with_untracked_q_loads_spill_nothing(tmp_path):
 
 
 @needs_tools
+def test_split_kv_attention_kernels_spill_nothing(tmp_path):
+    """attn_splitkv_kernel<APPEND> (decode and continuation) loads its Q fragments with ssdk::gload16_async and walks the
+    keys behind a hand-counted vmcnt: both instantiations of the walk kernel must exist and use no scratch."""
+    assert "gload16_async" in (build.CSRC / "attn_splitkv.hip").read_text()
+    md = kernel_metadata("attn_splitkv.hip", tmp_path)
+    walk = {k: v for k, v in md.items() if "attn_splitkv_kernel" in k}
+    assert sorted(re.search(r"ILb(\d)E", k).group(1) for k in walk) == ["0", "1"], list(md)
+    for k, v in walk.items():
+        assert v.get("private_segment_fixed_size") == 0 and v.get("vgpr_spill_count", 0) == 0, (k, v)
+
+
+@needs_tools
 def test_gemm_kernels_spill_nothing(tmp_path):
     """Both GEMM kernels keep five half-tiles of LDS-DMA copies in flight behind hand-counted waits and, at two waves per
     SIMD, live within 256 registers: a spill would put scratch loads — which the compiler waits for with vmcnt(0) — into

@@ -815,17 +815,6 @@ __global__ __launch_bounds__(512) void flash_fwd_stream_kernel(AttnArgs a) {
 
 std::atomic<int> g_fa_variant{[] { const char* v = getenv("TV_FA_W64"); return v ? atoi(v) : 0; }()};
 
-int tv_cu_count() {
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-      cus = 256;                               // MI355X
-    return cus;
-  }();
-  return n;
-}
-
 template <typename T, int KS, int DT>
 int launch_fa_d(const AttnArgs& a, int B, hipStream_t st) {
   constexpr int KT = FA_KT;

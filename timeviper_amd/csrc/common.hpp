@@ -71,6 +71,18 @@ __device__ __forceinline__ float wave_incl_scan(float v) {
   return v;
 }
 
+// compute units of the current device (host; queried once)
+inline int tv_cu_count() {
+  static const int n = [] {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
+      cus = 256;                               // MI355X
+    return cus;
+  }();
+  return n;
+}
+
 // error plumbing (capi.cpp)
 void tv_set_error(const char* fmt, ...);
 #define TV_CHECK_ARG(cond, ...)                         \

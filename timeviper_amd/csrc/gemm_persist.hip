@@ -383,6 +383,8 @@ int launch(const PArgs& pa, int grid, hipStream_t st) {
   TV_LAUNCH_CHECK();
 }
 
+// (not common.hpp's tv_cu_count(): that one takes a count below 8 for a failed query and answers 256; here any positive
+// count stands, because grid_size() rounds to a multiple of 8 with a floor of 8 itself)
 int cu_count() {
   static const int n = [] {
     int dev = 0, cus = 0;

@@ -567,17 +567,6 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_reg_kernel(GemvArgs a)
   }
 }
 
-int cu_count() {
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-      cus = 256;                               // MI355X
-    return cus;
-  }();
-  return n;
-}
-
 // dev switches (A/B runs): TV_GEMV_NT = 0 plain loads of W; TV_GEMV_WGS = work-groups per CU (default 2)
 int gemv_nt() { static const int v = [] { const char* e = getenv("TV_GEMV_NT"); return e ? atoi(e) : 1; }(); return v; }
 int gemv_wgs() { static const int v = [] { const char* e = getenv("TV_GEMV_WGS"); return e ? atoi(e) : 2; }(); return v < 1 ? 1 : v; }
@@ -593,7 +582,7 @@ int launch_gemv_r(const GemvArgs& a, hipStream_t st) {
   }
   // two work-groups per CU; fewer when there are not R rows for each
   int wgs = (a.N + R - 1) / R;
-  const int most = gemv_wgs() * cu_count();
+  const int most = gemv_wgs() * tv_cu_count();
   if (wgs > most) wgs = most;
   gemv_bf16_kernel<PRO, MT, R, NB, NT, PF><<<dim3((unsigned)wgs), GV_THREADS, lds, st>>>(a);
   TV_LAUNCH_CHECK();
@@ -608,7 +597,7 @@ int launch_gemv_rows(const GemvArgs& a, hipStream_t st) {
     return TV_ERR_LAUNCH;
   }
   int wgs = (a.N + R * GV_WAVES - 1) / (R * GV_WAVES);            // >= one row group per wave, two work-groups per CU
-  const int most = gemv_wgs() * cu_count();
+  const int most = gemv_wgs() * tv_cu_count();
   if (wgs > most) wgs = most;
   gemv_rows_kernel<PRO, MT, NT, R, NB><<<dim3((unsigned)wgs), GV_THREADS, lds, st>>>(a);
   TV_LAUNCH_CHECK();
@@ -616,7 +605,7 @@ int launch_gemv_rows(const GemvArgs& a, hipStream_t st) {
 template <int PRO, bool NT>
 int launch_splitk_reg(const GemvArgs& a, hipStream_t st) {
   int wgs = (a.N + 1) / 2;
-  const int most = gemv_wgs() * cu_count();
+  const int most = gemv_wgs() * tv_cu_count();
   if (wgs > most) wgs = most;
   const int pw = a.K / 8 / GV_WAVES;                 // (reg_takes: K / 8 is a multiple of the four waves)
   if (pw == 64 * 5) gemv_splitk_reg_kernel<PRO, 2, 5, NT, true><<<dim3((unsigned)wgs), GV_THREADS, 0, st>>>(a);          // K = 10 240

@@ -89,6 +89,28 @@ __device__ __forceinline__ float wave_incl_scan_dpp(float v) {
   v += dpp_shift<0x143, 0xc>(v);   // row_bcast:31 -> rows 2,3
   return v;
 }
+// max / sum of a value with its copies in lanes l ^ 16 and l ^ 32 (v_permlane16_swap / v_permlane32_swap, no LDS): both
+// applied, the 4 lanes l % 16 + 16 g of a wave hold the same result
+__device__ __forceinline__ float xor16_max(float x) {
+  const unsigned u = __float_as_uint(x);
+  const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float xor32_max(float x) {
+  const unsigned u = __float_as_uint(x);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float xor16_sum(float x) {
+  const unsigned u = __float_as_uint(x);
+  const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float xor32_sum(float x) {
+  const unsigned u = __float_as_uint(x);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
 // softplus on the hardware exp/log units; the small-argument branch keeps full relative
 // accuracy where 1+e^x would round (log1p(e) = e - e^2/2 + O(e^3))
 __device__ __forceinline__ float softplus_fast(float x) {

@@ -287,6 +287,35 @@ int tv_selective_state_update_seq(void* state, const void* x, const void* dt, co
  * per row (other d_state, or B / C not aligned for the vector loads); 0 before the first call */
 int tv_selective_state_update_seq_last_impl(void);
 
+/* Speculative step (a draft to verify, of which only a prefix may be kept): ONE launch with two phases, either of
+ * which may be empty.  The state in memory is always the COMMITTED state.
+ *   commit: every state row is read once and advanced by the first n_commit tokens of the PREVIOUS step's operands
+ *           (x_prev, dt_prev, B_prev, C_prev: t_prev tokens, strides p* as below) without computing y; the row is
+ *           written back iff n_commit > 0;
+ *   verify: the march continues in registers over the t_new tokens of x / dt / Bm / Cm and writes their y; the state
+ *           these tokens lead to is NOT stored.
+ * n_commit: a host int in [0, t_prev] (anything else: TV_ERR_ARG), or, when n_commit_dev is non-null, one int32 in
+ * device memory read by the kernel and clamped to [0, t_prev] — what a captured graph replays with.  t_new == 0 is the
+ * flush of a finished speculation; t_prev == 0 or n_commit == 0 with t_new > 0 a pure look-ahead.  Operand layouts,
+ * strides, dt clamp, group_map, dispatch (lanes share a row for d_state 16 / 32 / 64 / 128 / 256, else a thread per
+ * row) and — bit for bit — the per-token arithmetic are those of tv_selective_state_update_seq: the state after the
+ * call is what that entry point leaves over the first n_commit previous tokens, y what it returns over the new tokens
+ * from that state.  Purely additive: tv_abi_version() stays 13 (no existing signature changed). */
+int tv_selective_state_update_spec(void* state, const void* A, const void* D, const void* dt_bias,
+                                   const void* x_prev, const void* dt_prev, const void* B_prev, const void* C_prev,
+                                   int t_prev, int n_commit, const int* n_commit_dev, int64_t px_stride_b,
+                                   int64_t px_stride_l, int64_t pdt_stride_b, int64_t pdt_stride_l,
+                                   int64_t pb_stride_b, int64_t pb_stride_l, int64_t pb_stride_g,
+                                   int64_t pc_stride_b, int64_t pc_stride_l, int64_t pc_stride_g,
+                                   const void* x, const void* dt, const void* Bm, const void* Cm, void* y, int t_new,
+                                   int64_t x_stride_b, int64_t x_stride_l, int64_t dt_stride_b, int64_t dt_stride_l,
+                                   int64_t b_stride_b, int64_t b_stride_l, int64_t b_stride_g, int64_t c_stride_b,
+                                   int64_t c_stride_l, int64_t c_stride_g, int64_t y_stride_b, int64_t y_stride_l,
+                                   int batch, int nheads, int headdim, int ngroups, int dstate, int dtype,
+                                   int dt_softplus, float dt_min, float dt_max, int group_map, void* stream);
+/* as tv_selective_state_update_seq_last_impl, for tv_selective_state_update_spec */
+int tv_selective_state_update_spec_last_impl(void);
+
 /* ------------------------------------------------------------------------
  * ViT linears with fused epilogues: C = epilogue(A . W^T), A (M,K), W (N,K) =
  * nn.Linear.weight as stored, C (M,N), all bf16 row-major with element row strides lda / ldw / ldc.

@@ -44,6 +44,9 @@ SIGNATURES = {
     "tv_selective_state_update": (_i, [_p] * 9 + [_i] * 7 + [_p]),
     "tv_selective_state_update_seq": (_i, [_p] * 9 + [_i] * 6 + [_l] * 12 + [_i, _i, _f, _f, _i, _p]),
     "tv_selective_state_update_seq_last_impl": (_i, []),
+    "tv_selective_state_update_spec": (_i, [_p] * 8 + [_i, _i, _p] + [_l] * 10 + [_p] * 5 + [_i] + [_l] * 12
+                                       + [_i] * 7 + [_f, _f, _i, _p]),
+    "tv_selective_state_update_spec_last_impl": (_i, []),
     "tv_attn_append_workspace_bytes": (_z, [_i] * 5),
     "tv_attn_append_fwd": (_i, [_p] * 5 + [_i, _i, _i, _p, _i, _i, _i] + [_l] * 12 + [_f, _i, _p, _z, _p]),
     "tv_attn_append_calls": (_i, []),

@@ -264,10 +264,122 @@ struct SeqArgs {
 
 constexpr int SQ_PF = 4;      // tokens whose operands are in flight while the previous SQ_PF are computed
 
+// dt of a token as the recurrence uses it — one definition for every kernel below, so that a state carried by one of them
+// and a state carried by another agree bit for bit
+__device__ __forceinline__ float seq_dt(float raw, float bias, int softplus, float dt_min, float dt_max) {
+  float d = raw + bias;
+  if (softplus) d = softplus_f(d);
+  return fminf(fmaxf(d, dt_min), dt_max);
+}
+
+// One token of the recurrence on a lane's 4 state entries.  WITH_Y: also the lane's part of y (before the sum over the
+// row's lanes); without it (the commit phase of the speculative kernel) C is never touched and its loads fold away.
+template <bool WITH_Y, typename V4>
+__device__ __forceinline__ float seq_token_step(f32x4& sv, float d, float av, float xr, const V4& Bv, const V4& Cv) {
+  const float dec = expf(d * av);
+  const float xv = d * xr;
+  float part = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    sv[i] = fmaf(dec, sv[i], xv * to_f32(Bv[i]));
+    if (WITH_Y) part = fmaf(sv[i], to_f32(Cv[i]), part);
+  }
+  return part;
+}
+
+template <typename T, typename V4>
+struct SeqBatch {
+  T dt[SQ_PF], x[SQ_PF];
+  V4 B[SQ_PF], C[SQ_PF];
+};
+
+// the per-row operand pointers of one token run (lane's piece of B / C, the row's x and dt) and their token strides
+template <typename T>
+struct SeqRun {
+  const T *xp, *dp, *Bp, *Cp;
+  int64_t xsl, dsl, bsl, csl;
+};
+
+struct SeqOps {               // one set of token operands as the entry points take them
+  const void *x, *dt, *Bm, *Cm;
+  int64_t xsb, xsl, dsb, dsl, bsb, bsl, bsg, csb, csl, csg;
+};
+
+template <typename T>
+__device__ __forceinline__ SeqRun<T> seq_run_of(const SeqOps& o, int b, int h, int p, int g, int P, int ln4) {
+  SeqRun<T> r;
+  r.xp = (const T*)o.x + (int64_t)b * o.xsb + (int64_t)h * P + p;
+  r.dp = (const T*)o.dt + (int64_t)b * o.dsb + h;
+  r.Bp = (const T*)o.Bm + (int64_t)b * o.bsb + (int64_t)g * o.bsg + ln4;
+  r.Cp = (const T*)o.Cm + (int64_t)b * o.csb + (int64_t)g * o.csg + ln4;
+  r.xsl = o.xsl; r.dsl = o.dsl; r.bsl = o.bsl; r.csl = o.csl;
+  return r;
+}
+
+// requests the operands of tokens t0 .. t0 + SQ_PF - 1 of a run of n >= 1 tokens (past the end: the last token again, never used)
+template <bool WITH_Y, typename T, typename V4>
+__device__ __forceinline__ void seq_load(SeqBatch<T, V4>& r, const SeqRun<T>& s, int t0, int n) {
+#pragma unroll
+  for (int j = 0; j < SQ_PF; ++j) {
+    const int64_t t = min(t0 + j, n - 1);
+    r.dt[j] = s.dp[t * s.dsl];
+    r.x[j] = s.xp[t * s.xsl];
+    r.B[j] = *(const V4*)(s.Bp + t * s.bsl);
+    if (WITH_Y) r.C[j] = *(const V4*)(s.Cp + t * s.csl);
+  }
+}
+
+struct SeqConsts {
+  float av, bv, dv, dt_min, dt_max;
+  int softplus;
+};
+
+// n >= 1 tokens against the row in `sv`; `cur` holds the operands of tokens 0 .. SQ_PF - 1 already.  Every branch on the
+// token count is wave-uniform (n is a launch argument, or one value read by the whole grid).
+template <bool WITH_Y, typename T, int LPR, typename V4>
+__device__ __forceinline__ void seq_march(f32x4& sv, SeqBatch<T, V4>& cur, const SeqRun<T>& s, int n, const SeqConsts& c,
+                                          T* yp, int64_t ysl, bool ok, int ln) {
+  SeqBatch<T, V4> nxt;
+  for (int t0 = 0; t0 < n; t0 += SQ_PF) {
+    seq_load<WITH_Y>(nxt, s, t0 + SQ_PF, n);
+#pragma unroll
+    for (int j = 0; j < SQ_PF; ++j) {
+      if (t0 + j < n) {                                 // wave-uniform
+        const float d = seq_dt(to_f32(cur.dt[j]), c.bv, c.softplus, c.dt_min, c.dt_max);
+        const float xr = to_f32(cur.x[j]);
+        float part = seq_token_step<WITH_Y>(sv, d, c.av, xr, cur.B[j], cur.C[j]);
+        if (WITH_Y) {
+          part = group_sum_dpp<LPR>(part);
+          if (ok && ln == LPR - 1) yp[(int64_t)(t0 + j) * ysl] = from_f32<T>(fmaf(c.dv, xr, part));
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SQ_PF; ++j) {
+      cur.dt[j] = nxt.dt[j];
+      cur.x[j] = nxt.x[j];
+      cur.B[j] = nxt.B[j];
+      if (WITH_Y) cur.C[j] = nxt.C[j];
+    }
+  }
+}
+
+template <typename T> struct seq_vec4 { typedef f16x4 type; };
+template <> struct seq_vec4<float> { typedef f32x4 type; };
+template <> struct seq_vec4<bf16_t> { typedef bf16x4 type; };
+
+__device__ __forceinline__ SeqOps seq_ops_of(const SeqArgs& a) {
+  SeqOps o;
+  o.x = a.x; o.dt = a.dt; o.Bm = a.Bm; o.Cm = a.Cm;
+  o.xsb = a.xsb; o.xsl = a.xsl; o.dsb = a.dsb; o.dsl = a.dsl; o.bsb = a.bsb; o.bsl = a.bsl; o.bsg = a.bsg;
+  o.csb = a.csb; o.csl = a.csl; o.csg = a.csg;
+  return o;
+}
+
 template <typename T, int LPR>
 __global__ __launch_bounds__(256) void state_update_seq_kernel(SeqArgs a) {
   constexpr int N = 4 * LPR, RPW = 64 / LPR, WAVES = 4;
-  typedef typename std::conditional<std::is_same<T, float>::value, f32x4, typename std::conditional<std::is_same<T, bf16_t>::value, bf16x4, f16x4>::type>::type vec4_t;
+  typedef typename seq_vec4<T>::type vec4_t;
   const int lane = threadIdx.x & 63;
   const int w = (int)blockIdx.x * WAVES + (threadIdx.x >> 6);
   const int sub = lane / LPR, ln = lane % LPR;
@@ -280,61 +392,16 @@ __global__ __launch_bounds__(256) void state_update_seq_kernel(SeqArgs a) {
   const int h = bh - b * a.H;
   const int g = a.group_map ? (h % a.G) : (int)((unsigned)h / (unsigned)(a.H / a.G));
   f32x4 sv = __builtin_nontemporal_load((const f32x4*)(a.state + (int64_t)rc * N) + ln);
-  const float av = a.A[h];
-  const float bv = a.dt_bias ? a.dt_bias[h] : 0.f;
-  const float dv = a.D ? a.D[h] : 0.f;
-  const T* xp = (const T*)a.x + (int64_t)b * a.xsb + (int64_t)h * a.P + p;
-  const T* dp = (const T*)a.dt + (int64_t)b * a.dsb + h;
-  const T* Bp = (const T*)a.Bm + (int64_t)b * a.bsb + (int64_t)g * a.bsg + 4 * ln;
-  const T* Cp = (const T*)a.Cm + (int64_t)b * a.csb + (int64_t)g * a.csg + 4 * ln;
+  SeqConsts c;
+  c.av = a.A[h];
+  c.bv = a.dt_bias ? a.dt_bias[h] : 0.f;
+  c.dv = a.D ? a.D[h] : 0.f;
+  c.dt_min = a.dt_min; c.dt_max = a.dt_max; c.softplus = a.softplus;
+  const SeqRun<T> s = seq_run_of<T>(seq_ops_of(a), b, h, p, g, a.P, 4 * ln);
   T* yp = (T*)a.y + (int64_t)b * a.ysb + (int64_t)h * a.P + p;
-
-  T dtc[SQ_PF], xc[SQ_PF], dtn[SQ_PF], xn[SQ_PF];
-  vec4_t Bc[SQ_PF], Cc[SQ_PF], Bn[SQ_PF], Cn[SQ_PF];
-#pragma unroll
-  for (int j = 0; j < SQ_PF; ++j) {
-    const int64_t t = min(j, a.T - 1);                  // (past the end: the last token again, never used)
-    dtc[j] = dp[t * a.dsl];
-    xc[j] = xp[t * a.xsl];
-    Bc[j] = *(const vec4_t*)(Bp + t * a.bsl);
-    Cc[j] = *(const vec4_t*)(Cp + t * a.csl);
-  }
-  for (int t0 = 0; t0 < a.T; t0 += SQ_PF) {
-#pragma unroll
-    for (int j = 0; j < SQ_PF; ++j) {
-      const int64_t t = min(t0 + SQ_PF + j, a.T - 1);
-      dtn[j] = dp[t * a.dsl];
-      xn[j] = xp[t * a.xsl];
-      Bn[j] = *(const vec4_t*)(Bp + t * a.bsl);
-      Cn[j] = *(const vec4_t*)(Cp + t * a.csl);
-    }
-#pragma unroll
-    for (int j = 0; j < SQ_PF; ++j) {
-      if (t0 + j < a.T) {                               // wave-uniform
-        float d = to_f32(dtc[j]) + bv;
-        if (a.softplus) d = softplus_f(d);
-        d = fminf(fmaxf(d, a.dt_min), a.dt_max);
-        const float dec = expf(d * av);
-        const float xr = to_f32(xc[j]);
-        const float xv = d * xr;
-        float part = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          sv[i] = fmaf(dec, sv[i], xv * to_f32(Bc[j][i]));
-          part = fmaf(sv[i], to_f32(Cc[j][i]), part);
-        }
-        part = group_sum_dpp<LPR>(part);
-        if (ok && ln == LPR - 1) yp[(int64_t)(t0 + j) * a.ysl] = from_f32<T>(fmaf(dv, xr, part));
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < SQ_PF; ++j) {
-      dtc[j] = dtn[j];
-      xc[j] = xn[j];
-      Bc[j] = Bn[j];
-      Cc[j] = Cn[j];
-    }
-  }
+  SeqBatch<T, vec4_t> cur;
+  seq_load<true>(cur, s, 0, a.T);
+  seq_march<true, T, LPR>(sv, cur, s, a.T, c, yp, a.ysl, ok, ln);
   if (ok) __builtin_nontemporal_store(sv, (f32x4*)(a.state + (int64_t)row * N) + ln);
 }
 
@@ -349,9 +416,8 @@ __global__ void state_update_seq_rows_kernel(SeqArgs a) {
   const float Ah = a.A[h], bias = a.dt_bias ? a.dt_bias[h] : 0.f, Dh = a.D ? a.D[h] : 0.f;
   float* s = a.state + (((int64_t)b * a.H + h) * a.P + p) * N;
   for (int t = 0; t < a.T; ++t) {
-    float d = to_f32(((const T*)a.dt)[(int64_t)b * a.dsb + (int64_t)t * a.dsl + h]) + bias;
-    if (a.softplus) d = softplus_f(d);
-    d = fminf(fmaxf(d, a.dt_min), a.dt_max);
+    const float d = seq_dt(to_f32(((const T*)a.dt)[(int64_t)b * a.dsb + (int64_t)t * a.dsl + h]), bias, a.softplus,
+                           a.dt_min, a.dt_max);
     const float dec = expf(d * Ah);
     const float xr = to_f32(((const T*)a.x)[(int64_t)b * a.xsb + (int64_t)t * a.xsl + (int64_t)h * a.P + p]);
     const float xv = d * xr;
@@ -364,6 +430,135 @@ __global__ void state_update_seq_rows_kernel(SeqArgs a) {
       acc = fmaf(v, to_f32(Cr[n]), acc);
     }
     ((T*)a.y)[(int64_t)b * a.ysb + (int64_t)t * a.ysl + (int64_t)h * a.P + p] = from_f32<T>(fmaf(Dh, xr, acc));
+  }
+}
+
+// ---------------------------------------------------------------- speculation: commit the kept tokens, look ahead
+// One launch per Mamba layer and draft-and-verify step.  The state in memory is always the COMMITTED state: tokens fed
+// provisionally (a draft that may be rejected) never reach it.
+//   commit phase: the row advances by the first n_commit of the PREVIOUS step's tokens (their operands were kept by the
+//                 caller) — the token step of the sequence kernel without y — and is stored iff n_commit > 0;
+//   verify phase: the march goes on in registers over the T_new tokens of this step and writes their y; nothing of it
+//                 is stored.
+// A step therefore reads the state once and writes it at most once, as a decode step does.  n_commit is a launch
+// argument or, for a captured graph, one int the whole grid reads (clamped to [0, T_prev]: a stale value cannot reach
+// past the kept operands); every branch on it is wave-uniform.  The first operands of the verify phase are requested in
+// front of the commit phase, beside the state row: their latency hides behind it.
+struct SpecArgs {
+  SeqArgs a;                  // the new tokens: operands, y, T = T_new, and everything per layer
+  SeqOps prev;                // the previous step's operands
+  int T_prev, n_commit;
+  const int* n_commit_dev;
+};
+
+__device__ __forceinline__ int spec_n_commit(const SpecArgs& s) {
+  return s.n_commit_dev ? min(max(*s.n_commit_dev, 0), s.T_prev) : s.n_commit;
+}
+
+template <typename T, int LPR>
+__global__ __launch_bounds__(256) void state_update_spec_kernel(SpecArgs sa) {
+  constexpr int N = 4 * LPR, RPW = 64 / LPR, WAVES = 4;
+  typedef typename seq_vec4<T>::type vec4_t;
+  const SeqArgs& a = sa.a;
+  const int lane = threadIdx.x & 63;
+  const int w = (int)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  const int sub = lane / LPR, ln = lane % LPR;
+  const int row = w * RPW + sub;
+  const bool ok = row < a.rows_total;
+  const int rc = ok ? row : a.rows_total - 1;
+  const int bh = (int)((unsigned)rc / (unsigned)a.P);
+  const int p = rc - bh * a.P;
+  const int b = (int)((unsigned)bh / (unsigned)a.H);
+  const int h = bh - b * a.H;
+  const int g = a.group_map ? (h % a.G) : (int)((unsigned)h / (unsigned)(a.H / a.G));
+  f32x4 sv = __builtin_nontemporal_load((const f32x4*)(a.state + (int64_t)rc * N) + ln);
+  const int nc = spec_n_commit(sa);
+  SeqConsts c;
+  c.av = a.A[h];
+  c.bv = a.dt_bias ? a.dt_bias[h] : 0.f;
+  c.dv = a.D ? a.D[h] : 0.f;
+  c.dt_min = a.dt_min; c.dt_max = a.dt_max; c.softplus = a.softplus;
+  SeqRun<T> sn = {};
+  SeqBatch<T, vec4_t> curn = {};
+  if (a.T > 0) {
+    sn = seq_run_of<T>(seq_ops_of(a), b, h, p, g, a.P, 4 * ln);
+    seq_load<true>(curn, sn, 0, a.T);
+  }
+  if (nc > 0) {
+    const SeqRun<T> sp = seq_run_of<T>(sa.prev, b, h, p, g, a.P, 4 * ln);
+    SeqBatch<T, vec4_t> curp;
+    seq_load<false>(curp, sp, 0, nc);
+    seq_march<false, T, LPR>(sv, curp, sp, nc, c, (T*)nullptr, 0, ok, ln);
+    if (ok) __builtin_nontemporal_store(sv, (f32x4*)(a.state + (int64_t)row * N) + ln);
+  }
+  if (a.T > 0) {
+    T* yp = (T*)a.y + (int64_t)b * a.ysb + (int64_t)h * a.P + p;
+    seq_march<true, T, LPR>(sv, curn, sn, a.T, c, yp, a.ysl, ok, ln);
+  }
+}
+
+// any d_state, a thread per row.  Commit: the row is walked in memory once per kept token, as the sequence kernel walks
+// it.  Verify: the row must stay as committed, and a thread cannot hold a row of any length in registers: the loops are
+// turned inside out — per state entry n the march over the tokens runs in one register, and y of SR_TC tokens at a time
+// is accumulated over n in ascending order (the order, and so the rounding, of the sequence kernel's sum).  Tokens in
+// front of the current SR_TC are marched again per entry: quadratic in T_new / SR_TC, on a path that exists for
+// correctness at unusual d_state, not for speed.
+constexpr int SR_TC = 8;
+
+template <typename T>
+__global__ void state_update_spec_rows_kernel(SpecArgs sa) {
+  const SeqArgs& a = sa.a;
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const int h = blockIdx.y, b = blockIdx.z;
+  if (p >= a.P) return;
+  const int N = a.N;
+  const int g = a.group_map ? (h % a.G) : h / (a.H / a.G);
+  const float Ah = a.A[h], bias = a.dt_bias ? a.dt_bias[h] : 0.f, Dh = a.D ? a.D[h] : 0.f;
+  float* s = a.state + (((int64_t)b * a.H + h) * a.P + p) * N;
+  const int nc = spec_n_commit(sa);
+  const SeqOps& o = sa.prev;
+  for (int t = 0; t < nc; ++t) {
+    const float d = seq_dt(to_f32(((const T*)o.dt)[(int64_t)b * o.dsb + (int64_t)t * o.dsl + h]), bias, a.softplus,
+                           a.dt_min, a.dt_max);
+    const float dec = expf(d * Ah);
+    const float xr = to_f32(((const T*)o.x)[(int64_t)b * o.xsb + (int64_t)t * o.xsl + (int64_t)h * a.P + p]);
+    const float xv = d * xr;
+    const T* Br = (const T*)o.Bm + (int64_t)b * o.bsb + (int64_t)t * o.bsl + (int64_t)g * o.bsg;
+    for (int n = 0; n < N; ++n) s[n] = fmaf(dec, s[n], xv * to_f32(Br[n]));
+  }
+  const T* xb = (const T*)a.x + (int64_t)b * a.xsb + (int64_t)h * a.P + p;
+  const T* db = (const T*)a.dt + (int64_t)b * a.dsb + h;
+  const T* Bb = (const T*)a.Bm + (int64_t)b * a.bsb + (int64_t)g * a.bsg;
+  const T* Cb = (const T*)a.Cm + (int64_t)b * a.csb + (int64_t)g * a.csg;
+  for (int c0 = 0; c0 < a.T; c0 += SR_TC) {
+    float dec[SR_TC], xv[SR_TC], xr[SR_TC], acc[SR_TC];
+#pragma unroll
+    for (int j = 0; j < SR_TC; ++j) {
+      const int64_t t = min(c0 + j, a.T - 1);
+      const float d = seq_dt(to_f32(db[t * a.dsl]), bias, a.softplus, a.dt_min, a.dt_max);
+      dec[j] = expf(d * Ah);
+      xr[j] = to_f32(xb[t * a.xsl]);
+      xv[j] = d * xr[j];
+      acc[j] = 0.f;
+    }
+    for (int n = 0; n < N; ++n) {
+      float v = s[n];
+      for (int t = 0; t < c0; ++t) {                    // the tokens in front of this batch, again
+        const float d = seq_dt(to_f32(db[(int64_t)t * a.dsl]), bias, a.softplus, a.dt_min, a.dt_max);
+        v = fmaf(expf(d * Ah), v, (d * to_f32(xb[(int64_t)t * a.xsl])) * to_f32(Bb[(int64_t)t * a.bsl + n]));
+      }
+#pragma unroll
+      for (int j = 0; j < SR_TC; ++j) {
+        if (c0 + j < a.T) {
+          v = fmaf(dec[j], v, xv[j] * to_f32(Bb[(int64_t)(c0 + j) * a.bsl + n]));
+          acc[j] = fmaf(v, to_f32(Cb[(int64_t)(c0 + j) * a.csl + n]), acc[j]);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SR_TC; ++j)
+      if (c0 + j < a.T)
+        ((T*)a.y)[(int64_t)b * a.ysb + (int64_t)(c0 + j) * a.ysl + (int64_t)h * a.P + p] = from_f32<T>(fmaf(Dh, xr[j], acc[j]));
   }
 }
 
@@ -499,6 +694,82 @@ extern "C" int tv_selective_state_update_seq(void* state, const void* x, const v
     case TV_F32: state_update_seq_rows_kernel<float><<<grid, 64, 0, s>>>(a); break;
     case TV_BF16: state_update_seq_rows_kernel<bf16_t><<<grid, 64, 0, s>>>(a); break;
     default: state_update_seq_rows_kernel<f16_t><<<grid, 64, 0, s>>>(a); break;
+  }
+  TV_LAUNCH_CHECK();
+}
+
+static int g_spec_last_impl = 0;
+extern "C" int tv_selective_state_update_spec_last_impl(void) { return g_spec_last_impl; }
+
+extern "C" int tv_selective_state_update_spec(
+    void* state, const void* A, const void* D, const void* dt_bias,
+    const void* x_prev, const void* dt_prev, const void* B_prev, const void* C_prev, int t_prev, int n_commit,
+    const int* n_commit_dev, int64_t pxsb, int64_t pxsl, int64_t pdsb, int64_t pdsl, int64_t pbsb, int64_t pbsl,
+    int64_t pbsg, int64_t pcsb, int64_t pcsl, int64_t pcsg,
+    const void* x, const void* dt, const void* Bm, const void* Cm, void* y, int t_new, int64_t xsb, int64_t xsl,
+    int64_t dsb, int64_t dsl, int64_t bsb, int64_t bsl, int64_t bsg, int64_t csb, int64_t csl, int64_t csg, int64_t ysb,
+    int64_t ysl, int batch, int nheads, int headdim, int ngroups, int dstate, int dtype, int dt_softplus, float dt_min,
+    float dt_max, int group_map, void* stream) {
+  TV_CHECK_ARG(state && A, "selective_state_update_spec: null pointer");
+  TV_CHECK_ARG(batch > 0 && t_prev >= 0 && t_new >= 0 && nheads > 0 && headdim > 0 && ngroups > 0 && dstate > 0 &&
+                   nheads % ngroups == 0,
+               "selective_state_update_spec: bad sizes");
+  TV_CHECK_ARG(t_prev == 0 || (x_prev && dt_prev && B_prev && C_prev), "selective_state_update_spec: null previous operands");
+  TV_CHECK_ARG(t_new == 0 || (x && dt && Bm && Cm && y), "selective_state_update_spec: null operands");
+  TV_CHECK_ARG(n_commit_dev || (n_commit >= 0 && n_commit <= t_prev),
+               "selective_state_update_spec: n_commit outside [0, t_prev]");
+  const int64_t hp = (int64_t)nheads * headdim;
+  TV_CHECK_ARG(t_prev == 0 || (pxsl >= hp && pdsl >= nheads), "selective_state_update_spec: previous x / dt rows overlap");
+  TV_CHECK_ARG(t_new == 0 || (xsl >= hp && ysl >= hp && dsl >= nheads), "selective_state_update_spec: x / y / dt rows overlap");
+  if (dtype != TV_F32 && dtype != TV_BF16 && dtype != TV_F16) TV_UNSUPPORTED("selective_state_update_spec: dtype %d", dtype);
+  if (t_new == 0 && (t_prev == 0 || (!n_commit_dev && n_commit == 0))) return TV_OK;      // nothing to commit, nothing to run
+  hipStream_t s = (hipStream_t)stream;
+  SpecArgs sa;
+  SeqArgs& a = sa.a;
+  a.state = (float*)state; a.x = x; a.dt = dt; a.Bm = Bm; a.Cm = Cm;
+  a.A = (const float*)A; a.D = (const float*)D; a.dt_bias = (const float*)dt_bias; a.y = y;
+  a.T = t_new; a.H = nheads; a.P = headdim; a.G = ngroups; a.N = dstate;
+  a.xsb = xsb; a.xsl = xsl; a.dsb = dsb; a.dsl = dsl; a.bsb = bsb; a.bsl = bsl; a.bsg = bsg;
+  a.csb = csb; a.csl = csl; a.csg = csg; a.ysb = ysb; a.ysl = ysl;
+  a.softplus = dt_softplus; a.group_map = group_map; a.dt_min = dt_min; a.dt_max = dt_max;
+  SeqOps& o = sa.prev;
+  o.x = x_prev; o.dt = dt_prev; o.Bm = B_prev; o.Cm = C_prev;
+  o.xsb = pxsb; o.xsl = pxsl; o.dsb = pdsb; o.dsl = pdsl; o.bsb = pbsb; o.bsl = pbsl; o.bsg = pbsg;
+  o.csb = pcsb; o.csl = pcsl; o.csg = pcsg;
+  sa.T_prev = t_prev; sa.n_commit = n_commit_dev ? 0 : n_commit; sa.n_commit_dev = n_commit_dev;
+  const int64_t rows = (int64_t)batch * nheads * headdim;
+  a.rows_total = (int)(rows < (1ll << 31) ? rows : 0);
+  // as in the sequence entry point: the lanes of a row read 4 entries of B / C as one vector, of either operand set
+  const int lpr = dstate / 4;
+  int64_t bc = 0;
+  uintptr_t ptrs = (uintptr_t)0;
+  if (t_new > 0) { bc |= bsb | bsl | bsg | csb | csl | csg; ptrs |= (uintptr_t)Bm | (uintptr_t)Cm; }
+  if (t_prev > 0) { bc |= pbsb | pbsl | pbsg; ptrs |= (uintptr_t)B_prev; }
+  const uintptr_t bc_align = dtype == TV_F32 ? 15 : 7;
+  if (dstate % 4 == 0 && (lpr == 4 || lpr == 8 || lpr == 16 || lpr == 32 || lpr == 64) && (((uintptr_t)state) & 15) == 0 &&
+      (ptrs & bc_align) == 0 && bc % 4 == 0 && rows < (1ll << 31)) {
+    g_spec_last_impl = 1;
+    const int64_t rows_per_block = 4 * (64 / lpr);
+    const dim3 rgrid((unsigned)((rows + rows_per_block - 1) / rows_per_block));
+#define TV_SP(T, LPR) state_update_spec_kernel<T, LPR><<<rgrid, 256, 0, s>>>(sa)
+#define TV_SP_T(T)                                                                                          \
+    switch (lpr) { case 4: TV_SP(T, 4); break; case 8: TV_SP(T, 8); break; case 16: TV_SP(T, 16); break;       \
+                   case 32: TV_SP(T, 32); break; default: TV_SP(T, 64); break; }
+    switch (dtype) {
+      case TV_F32: TV_SP_T(float); break;
+      case TV_BF16: TV_SP_T(bf16_t); break;
+      default: TV_SP_T(f16_t); break;
+    }
+#undef TV_SP_T
+#undef TV_SP
+    TV_LAUNCH_CHECK();
+  }
+  g_spec_last_impl = 2;
+  dim3 grid((headdim + 63) / 64, nheads, batch);
+  switch (dtype) {
+    case TV_F32: state_update_spec_rows_kernel<float><<<grid, 64, 0, s>>>(sa); break;
+    case TV_BF16: state_update_spec_rows_kernel<bf16_t><<<grid, 64, 0, s>>>(sa); break;
+    default: state_update_spec_rows_kernel<f16_t><<<grid, 64, 0, s>>>(sa); break;
   }
   TV_LAUNCH_CHECK();
 }

@@ -493,6 +493,98 @@ def selective_state_update_seq_last_impl() -> int:
     return int(_capi.lib().tv_selective_state_update_seq_last_impl())
 
 
+def _seq_operands(name, x, dt, B, C, dtype=None):
+    """x (B,T,H,P), dt (B,T,H), B / C (B,T,G,N) as the sequence / speculative entry points take them: (tensors, strides)."""
+    Bsz, T, H, P = x.shape
+    dtype = x.dtype if dtype is None else dtype
+    if T < 1:
+        raise TimeViperHipError(f"{name}: at least one token")
+    x, dt, B, C = (t if t.dtype == dtype else t.to(dtype) for t in (x, dt, B, C))
+    x, xsb, xsl = _row_view(x, H * P)
+    dt, dsb, dsl = _row_view(dt, H)
+    B = B if B.stride(3) == 1 else B.contiguous()
+    C = C if C.stride(3) == 1 else C.contiguous()
+    return (x, dt, B, C), (xsb, xsl, dsb, dsl, B.stride(0), B.stride(1), B.stride(2), C.stride(0), C.stride(1), C.stride(2))
+
+
+def selective_state_update_spec(state, prev, n_commit, new, A, D=None, dt_bias=None, dt_softplus=False,
+                                dt_limit=(0.0, float("inf")), group_map="block", out=None):
+    """One speculative step against a resident state (tv_selective_state_update_spec): the state in memory advances by the
+    first `n_commit` tokens of `prev` — the operands (x, dt, B, C) of the previous step, or None — and y is computed for
+    the tokens of `new` = (x, dt, B, C) (or None: the flush) from there, WITHOUT storing the state they lead to.
+    `n_commit`: an int in [0, T_prev], or an int32 tensor of one element on the GPU (read by the kernel, clamped to that
+    range: what a captured graph replays with).  Layouts as `selective_state_update_seq`, whose bits this reproduces:
+    state as left by it over prev[:n_commit], y as returned by it over `new` from that state.  Returns y (B,T,H,P) or None."""
+    if prev is None and new is None:
+        return None
+    _gpu(state, A, D, dt_bias, *(prev or ()), *(new or ()))
+    ref = (new or prev)[0]
+    Bsz, _, H, P = ref.shape
+    G, N = (new or prev)[2].shape[2], (new or prev)[2].shape[3]
+    if state.dtype != torch.float32 or not state.is_contiguous() or state.shape != (Bsz, H, P, N):
+        raise TimeViperHipError("selective_state_update_spec: state must be contiguous fp32 (B, H, P, N)")
+    t_prev, t_new, pt, ps, nt, ns = 0, 0, (None,) * 4, (0,) * 10, (None,) * 4, (0,) * 10
+    if prev is not None:
+        pt, ps = _seq_operands("selective_state_update_spec", *prev, dtype=ref.dtype)
+        t_prev = pt[0].shape[1]
+    if new is not None:
+        nt, ns = _seq_operands("selective_state_update_spec", *new)
+        t_new = nt[0].shape[1]
+    if any(t is not None and (t.shape[0] != Bsz or t.shape[-1] != s) for ts in (pt, nt) for t, s in zip(ts, (P, H, N, N))):
+        raise TimeViperHipError("selective_state_update_spec: operand shapes disagree")
+    nc_dev = None
+    if isinstance(n_commit, torch.Tensor):
+        if n_commit.dtype != torch.int32 or n_commit.numel() != 1 or not n_commit.is_cuda:
+            raise TimeViperHipError("selective_state_update_spec: a device n_commit is one int32 on the GPU")
+        nc_dev, n_commit = n_commit, 0
+    elif not 0 <= int(n_commit) <= t_prev:
+        raise TimeViperHipError(f"selective_state_update_spec: n_commit {n_commit} outside [0, {t_prev}]")
+    f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()
+    A, D, dt_bias = f32(A), f32(D), f32(dt_bias)
+    y, ysb, ysl = None, 0, 0
+    if new is not None:
+        y = torch.empty((Bsz, t_new, H, P), dtype=ref.dtype, device=ref.device) if out is None else out
+        if y.shape != (Bsz, t_new, H, P) or y.dtype != ref.dtype or y.stride(3) != 1 or y.stride(2) != P or not y.is_cuda:
+            raise TimeViperHipError("selective_state_update_spec: out must be (B, T, H, P) of x's dtype with dense H * P rows")
+        ysb, ysl = y.stride(0), y.stride(1)
+    check(_capi.lib().tv_selective_state_update_spec(
+        _p(state), _p(A), _p(D), _p(dt_bias), *(_p(t) for t in pt), t_prev, int(n_commit), _p(nc_dev), *ps,
+        *(_p(t) for t in nt), _p(y), t_new, *ns, ysb, ysl, Bsz, H, P, G, N, _dt(ref), int(bool(dt_softplus)),
+        float(dt_limit[0]), float(min(dt_limit[1], 3.0e38)), {"block": 0, "tile": 1}[group_map], _stream()),
+        "tv_selective_state_update_spec")
+    return y
+
+
+def selective_state_update_spec_last_impl() -> int:
+    """1: the most recent `selective_state_update_spec` ran with lanes sharing a state row, 2: a thread per row."""
+    return int(_capi.lib().tv_selective_state_update_spec_last_impl())
+
+
+def causal_conv1d_xbc_into(xBC, weight, bias, d_inner: int, ngroups: int, dstate: int, out, activation="silu", halo=None):
+    """`causal_conv1d_xbc` writing into caller-owned storage: out = (x (B, L, d_inner), B, C (B, G, L, N)), contiguous —
+    operands that must stay at a fixed address (the speculative step keeps them for its next launch).  Returns x and
+    the (B, L, G, N) views of B and C."""
+    _gpu(xBC, weight, bias, halo, *out)
+    Bsz, L, Cc = xBC.shape
+    assert Cc == d_inner + 2 * ngroups * dstate
+    yx, yb, yc = out
+    if (yx.shape != (Bsz, L, d_inner) or yb.shape != (Bsz, ngroups, L, dstate) or yc.shape != yb.shape
+            or any(t.dtype != xBC.dtype or not t.is_contiguous() for t in out)):
+        raise TimeViperHipError("causal_conv1d_xbc_into: out must be contiguous (B, L, d_inner), (B, G, L, N), (B, G, L, N)")
+    if xBC.stride(2) != 1:
+        xBC = xBC.contiguous()
+    K = weight.shape[-1]
+    w = weight.reshape(Cc, K).to(xBC.dtype).contiguous()
+    b = None if bias is None else bias.to(xBC.dtype).contiguous()
+    if halo is not None:
+        halo = halo.to(xBC.dtype).contiguous()
+    check(_capi.lib().tv_causal_conv1d_xbc_fwd(
+        _p(xBC), _p(w), _p(b), _p(halo), _p(yx), _p(yb), _p(yc), Bsz, L, d_inner, ngroups, dstate,
+        K, xBC.stride(0), xBC.stride(1), _dt(xBC), int(activation in ("silu", "swish")), _stream()),
+        "tv_causal_conv1d_xbc_fwd")
+    return yx, yb.transpose(1, 2), yc.transpose(1, 2)
+
+
 def ssd_scan_set_impl(impl: int) -> None:
     """0 auto (= 6 where it applies, else 4, 3; other dtypes / d_state: 8, else 1), 1 generic fp32 token recurrence, 3 MFMA
     slice march on <= 40-column slices of a head, 4 whole-head slice march x sequence segments, 6 head-per-wave march

@@ -305,10 +305,13 @@ class GenericTimeViperVLM(nn.Module):
         llm = self.llm_backbone.llm
         cache = kwargs.pop("past_key_values", None)
         return_cache = bool(kwargs.pop("return_past_key_values", False))
+        speculative = kwargs.pop("speculative", None)
+        draft_fn = kwargs.pop("draft_fn", None)
         mi = self.prepare_inputs_for_generation(input_ids, past_key_values=None, attention_mask=attention_mask,
                                                 pixel_values=pixel_values, pixel_values_videos=pixel_values_videos,
                                                 answer_prompt=kwargs.pop("answer_prompt", None))
         pdargs = self.pdrop_args if self.use_pdrop else None
+        prompt_ids = mi["input_ids"]                       # (with the answer prompt: what the drafter looks drafts up in)
         if cache is None:
             cache = llm.new_cache(1, dtype=self.dtype, device=self.device)
             out = self.forward(input_ids=mi["input_ids"], pixel_values=mi["pixel_values"],
@@ -341,6 +344,13 @@ class GenericTimeViperVLM(nn.Module):
         new_tokens: List[int] = []
         fed = 0                               # how many of them went through the model
         tok = out.logits[:, -1].argmax(-1)
+        self.last_generate_stats = {"speculative": False, "steps": 0, "drafted": 0, "accepted": 0, "emitted": 0,
+                                    "graphed": False, "replays": 0, "graphs": 0, "capture_error": None}
+        n_drafts = self._speculative_drafts(speculative, cache, max_new_tokens)
+        if n_drafts:
+            history = [int(t) for t in prompt_ids.reshape(-1).tolist()]
+            new_tokens, fed = self._speculative_decode(cache, int(tok), n_drafts, draft_fn, history, max_new_tokens, eos, pdargs)
+            return self._finish_generate(new_tokens, fed, cache, return_ids, return_cache)
         stepper = self._graphed_decode_step(cache, max_new_tokens, pdargs)
         for _ in range(max_new_tokens):
             t = int(tok)
@@ -357,12 +367,97 @@ class GenericTimeViperVLM(nn.Module):
                                     cache_position=mi["cache_position"], position_ids=mi["position_ids"],
                                     train_pdrop_args=pdargs)
             tok = out.logits[:, -1].argmax(-1)
+        self.last_generate_stats.update(steps=fed, emitted=len(new_tokens), graphed=stepper is not None
+                                        and stepper.graph is not None)
+        return self._finish_generate(new_tokens, fed, cache, return_ids, return_cache)
+
+    def _finish_generate(self, new_tokens, fed, cache, return_ids, return_cache):
         ids = torch.tensor([new_tokens], device=self.device)
         cache.pending_ids = ids[:, fed:].clone()
         tokenizer = self.llm_backbone.tokenizer
         result = ids if return_ids or not hasattr(tokenizer, "decode") \
             else tokenizer.decode(ids[0], skip_special_tokens=False).strip()
         return (result, cache) if return_cache else result
+
+    def _speculative_drafts(self, speculative, cache, max_new_tokens) -> int:
+        """Drafts per step D for `generate(speculative=...)`, or 0 where the stack is out of the feature's scope and the
+        tokens are decoded plainly: anything but the Nemotron-H hybrid with its hybrid cache (Qwen2's rotary positions),
+        fp8 attention, on the GPU anything but bf16 with attention head_dim 128 and (D + 1) x Hq / Hkv <= 128 columns
+        (tv_attn_append_fwd with a device-side key count), TV_DECODE_GRAPH=0 there (an eager step of ~400 launches loses
+        more than the drafts win)."""
+        if speculative is None or speculative is False:
+            return 0
+        from .llm.nano import HybridMambaAttentionDynamicCache, NemotronHForCausalLM, continue_t_seq
+        from .llm.speculative import DEFAULT_DRAFTS
+        from .. import kernels as K
+        D = DEFAULT_DRAFTS if speculative is True else int(speculative)
+        if D < 1:
+            raise ValueError("generate(speculative=D): D >= 1 drafts per step")
+        llm = self.llm_backbone.llm
+        if (not isinstance(llm, NemotronHForCausalLM) or not isinstance(cache, HybridMambaAttentionDynamicCache)
+                or not cache.attention_layers or max_new_tokens < 2 or D + 1 > continue_t_seq() or K._ATTN_FP8["on"]
+                or llm.dtype not in (torch.bfloat16, torch.float32)):
+            return 0
+        if self.device.type == "cuda":
+            cfg = llm.config
+            if (llm.dtype != torch.bfloat16 or cache.key_cache[cache.attention_layers[0]].shape[-1] != 128
+                    or (D + 1) * (cfg.num_attention_heads // cfg.num_key_value_heads) > 128
+                    or os.environ.get("TV_DECODE_GRAPH", "1") == "0"):
+                return 0
+        return D
+
+    def _speculative_decode(self, cache, first, D, draft_fn, history, max_new_tokens, eos, pdargs):
+        """The draft-and-verify loop behind `generate(speculative=D)` (llm/speculative.py, llm/decode_graph.py): per step
+        ONE forward over [t0, d1 .. dD] against the cache in speculation mode — a captured graph on the GPU — and one read
+        of (k, p1 .. pT): p1 .. pk are emitted, t0 and the k - 1 drafts that equal p1 .. p(k-1) stay in the cache.
+        Returns (new ids, how many of them went through the model), the cache flushed and out of speculation mode."""
+        from .llm.decode_graph import GraphedSpecStep
+        from .llm.speculative import prompt_lookup_draft
+        if draft_fn is None:
+            placeholder = (int(self.default_token_id),)
+            draft_fn = lambda ids, n: prompt_lookup_draft(ids, n, exclude_ids=placeholder)
+        stats = self.last_generate_stats
+        stats["speculative"] = True
+        new_tokens, fed, T = [first], 0, D + 1
+        if first in eos:
+            stats["emitted"] = 1
+            return new_tokens, fed
+        cache.begin_speculation(T, max_new_tokens)
+        host_pos = torch.ones(1, dtype=torch.long)              # "not the prefill" for the mixers' host-side branch
+        dev_pos = torch.ones((1, 1), dtype=torch.long, device=self.device)
+
+        def step_fn(ids):
+            return self.llm_backbone(input_ids=ids, past_key_values=cache, use_cache=True, cache_position=host_pos,
+                                     position_ids=dev_pos, train_pdrop_args=pdargs, logits_to_keep=ids.shape[1]).logits
+        stepper = GraphedSpecStep(step_fn, cache, T, self.device, graphed=self.device.type == "cuda")
+        done = False
+        while not done:
+            drafts = [int(t) for t in draft_fn(history + new_tokens, D)][:D]
+            n_real = len(drafts)
+            drafts += [0] * (D - n_real)                          # padding can only be rejected or be right
+            k, p = stepper.step(new_tokens[-1], drafts)
+            stats["steps"] += 1
+            stats["drafted"] += n_real
+            stats["accepted"] += min(k - 1, n_real)
+            for m in range(1, k + 1):                             # p1 .. pk; t0 and d1 .. d(m-1) are fed and kept
+                new_tokens.append(p[m - 1])
+                fed += 1
+                if p[m - 1] in eos or len(new_tokens) >= max_new_tokens:
+                    if m < k:
+                        cache.commit(m)
+                    done = True
+                    break
+        if new_tokens[-1] not in eos:
+            # the length limit: the plain loop runs its last token through the model too (nothing is left pending)
+            with torch.inference_mode():
+                step_fn(torch.tensor([[new_tokens[-1]]], device=self.device))
+            cache.commit(1)
+            fed += 1
+        cache.end_speculation()
+        stats.update(emitted=len(new_tokens), graphed=bool(stepper.graphs) and stepper.capture_error is None,
+                     replays=stepper.replays, graphs=len(stepper.graphs),
+                     capture_error=None if stepper.capture_error is None else repr(stepper.capture_error))
+        return new_tokens, fed
 
     def _graphed_decode_step(self, cache, max_new_tokens, pdargs):
         """The decode step behind `generate` as a captured graph (llm/decode_graph.py) where the stack allows it: the

@@ -22,7 +22,7 @@ import warnings
 
 import torch
 
-__all__ = ["GraphedDecodeStep"]
+__all__ = ["GraphedDecodeStep", "GraphedSpecStep"]
 
 
 class GraphedDecodeStep:
@@ -93,3 +93,84 @@ class GraphedDecodeStep:
             self.graph = graph
             graph.replay()
         return self.next_ids
+
+
+class GraphedSpecStep:
+    """One draft-and-verify step of speculative greedy decoding as ONE hipGraph launch.
+
+    `step(t0, drafts)` feeds [t0, d1 .. dD] (T = D + 1 ids at a fixed address) through step_fn — a forward against
+    `cache`, which is in speculation mode, returning the logits of the T positions, (1, T, V) — and computes on the device
+    p = argmax, a = the number of leading drafts with d_i == p_i, k = a + 1, and `cache.commit(k)`.  It returns (k, p) to
+    the host with one read.  The cache keeps two operand slots per Mamba layer and flips them every forward, so there are
+    two graphs, one per slot parity: the first `warmup` calls run eagerly, the next two are captured, every later one
+    replays the graph of its parity.  A failed capture falls back to the eager step for the rest of the generation, as
+    GraphedDecodeStep does (`capture_error` holds the reason; out of memory is raised)."""
+
+    def __init__(self, step_fn: Callable[[torch.Tensor], torch.Tensor], cache, n_tokens: int, device, warmup: int = 2,
+                 graphed: bool = True):
+        if not getattr(cache, "speculating", False):
+            raise RuntimeError("GraphedSpecStep: call cache.begin_speculation(t_max, max_new_tokens) first")
+        self.step_fn, self.cache, self.T, self.warmup = step_fn, cache, int(n_tokens), int(warmup)
+        self.ids = torch.zeros((1, self.T), dtype=torch.int64, device=device)
+        self.graphed = bool(graphed)      # False: every step eager (the CPU, or a caller that wants no capture)
+        self.graphs, self.outs = {}, {}
+        self.capture_error = None
+        self.calls, self.replays = 0, 0
+
+    def _run(self):
+        logits = self.step_fn(self.ids)
+        p = logits.reshape(self.T, -1).argmax(-1)                                   # (T,)
+        k = self._accept(p)
+        self.cache.commit(k)
+        return torch.cat([k.reshape(1).to(torch.int64), p])
+
+    def _accept(self, p):
+        """k = 1 + the number of leading drafts that equal the model's own next token, on the device"""
+        a = (self.ids[0, 1:] == p[:-1]).to(torch.int32).cumprod(0).sum()
+        return (a + 1).to(torch.int32)
+
+    @torch.inference_mode()
+    def step(self, t0: int, drafts):
+        """-> (k, [p1 .. pT]): k tokens of the forward are kept (t0 and k - 1 drafts), p1 .. pk are the tokens to emit."""
+        host = torch.tensor([[int(t0)] + [int(d) for d in drafts]], dtype=torch.int64)
+        if host.shape[1] != self.T:
+            raise ValueError(f"GraphedSpecStep: {self.T - 1} drafts per step")
+        self.ids.copy_(host)
+        self.calls += 1
+        sp = self.cache._spec
+        parity = sp["flip"]
+        if parity in self.graphs:
+            self.cache.spec_check(self.T)
+            self.graphs[parity].replay()
+            self.cache.spec_replayed(self.T)
+            self.replays += 1
+            out = self.outs[parity]
+        elif not self.graphed or self.calls <= self.warmup or self.capture_error is not None:
+            out = self._run()
+        else:
+            saved = {k: sp[k] for k in ("flip", "t_prev", "done", "exact", "last_k", "last_exact")}
+            try:
+                side = torch.cuda.Stream(device=self.ids.device)
+                side.wait_stream(torch.cuda.current_stream())
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=side):
+                    out = self._run()
+                torch.cuda.current_stream().wait_stream(side)
+            except Exception as e:
+                self.capture_error = e
+                if isinstance(e, torch.cuda.OutOfMemoryError):
+                    raise
+                warnings.warn(f"speculative decode: graph capture failed ({type(e).__name__}: {e}); every further step runs "
+                              "as an eager sequence of launches (several times slower per step)", RuntimeWarning, stacklevel=2)
+                sp.update(saved)          # nothing of the capture executed: the host bookkeeping goes back
+                torch.cuda.synchronize()
+                out = self._run()
+            else:
+                # the capture ran the host bookkeeping of one step and no kernel: this replay is that step
+                self.graphs[parity], self.outs[parity] = graph, out
+                graph.replay()
+                self.replays += 1
+        res = out.tolist()
+        k = res[0]
+        self.cache.note_committed(k)
+        return k, res[1:]

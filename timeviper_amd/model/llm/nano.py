@@ -184,6 +184,10 @@ class HybridMambaAttentionDynamicCache:
         # ids `generate` emitted but has not run through the model yet (it stops before feeding its last token): the
         # next turn's continuation feeds them in front of its own ids
         self.pending_ids: Optional[torch.Tensor] = None
+        # speculation (begin_speculation): T tokens are taken provisionally, commit(k) keeps the first k
+        self._mamba_dims = (config.mamba_num_heads * config.mamba_head_dim, config.n_groups, config.ssm_state_size,
+                            config.mamba_num_heads)
+        self.speculating, self._spec = False, None
 
     def _reserve(self, layer_idx, need):
         have = self._kv_len[layer_idx]
@@ -276,6 +280,9 @@ class HybridMambaAttentionDynamicCache:
     def clone(self) -> "HybridMambaAttentionDynamicCache":
         """Deep copy of the conv / SSM states and of K / V at their current lengths (spare capacity is not copied, a
         static-decode mode is not inherited): one prefilled video forks into several questions."""
+        if getattr(self, "speculating", False):
+            raise RuntimeError("clone: the cache is in speculation mode (provisional tokens are not part of it yet); "
+                               "call end_speculation() first")
         new = object.__new__(type(self))
         new.__dict__.update({k: v for k, v in self.__dict__.items()
                              if k not in ("conv_states", "ssm_states", "key_cache", "value_cache", "_kv_buf", "_kv_len",
@@ -297,6 +304,171 @@ class HybridMambaAttentionDynamicCache:
         if getattr(self, "pdrop_args", None) is not None:
             new.pdrop_args = dict(self.pdrop_args)
         return new
+
+    # ---- speculation: T tokens per forward taken provisionally, the first k kept (see NemotronHMamba2Mixer._speculate)
+    def begin_speculation(self, t_max: int, max_new_tokens: int):
+        """Behind a prefill: from now on a forward of T <= t_max tokens leaves the conv / SSM states and the committed
+        K / V rows as they are, and `commit(k)` decides how many of its tokens the NEXT forward (or `end_speculation`) folds
+        in.  Memory holds the committed state at all times.  Per Mamba layer two slots keep a forward's operands (post-conv
+        x / B / C, the pre-conv rows and dt) — one being written, one holding the previous forward's; write position, key
+        count (the static-decode pairs, one per distinct length) and n_commit live on the device, so that a step has the same
+        launch parameters every time (GraphedSpecStep)."""
+        if self.speculating:
+            raise RuntimeError("begin_speculation: already speculating")
+        if not self.attention_layers or any(self._kv_len[i] == 0 for i in self.attention_layers):
+            raise RuntimeError("speculation starts behind a prefill (every attention layer holding its tokens)")
+        t_max, max_new_tokens = int(t_max), int(max_new_tokens)
+        if t_max < 1 or max_new_tokens < 0:
+            raise ValueError("begin_speculation: t_max >= 1, max_new_tokens >= 0")
+        self.end_static_decode()
+        for i in self.attention_layers:
+            self._reserve(i, self._kv_len[i] + max_new_tokens + t_max)
+        k0 = self.key_cache[self.attention_layers[0]]
+        dev, B = k0.device, k0.shape[0]
+        self._static = {n: (torch.full((1,), n, dtype=torch.int64, device=dev),
+                            torch.full((B,), n, dtype=torch.int32, device=dev))
+                        for n in sorted({self._kv_len[i] for i in self.attention_layers})}
+        self._static_of = {i: self._static[self._kv_len[i]] for i in self.attention_layers}
+        d_in, G, N, H = self._mamba_dims
+        slots = {}
+        for i, c in enumerate(self.hybrid_override_pattern):
+            if c == "M":
+                dt = self.conv_states[i].dtype
+                mk = lambda n: torch.zeros(B * t_max * n, dtype=dt, device=dev)
+                slots[i] = [{"x": mk(d_in), "B": mk(G * N), "C": mk(G * N), "tail": mk(d_in + 2 * G * N + H)} for _ in range(2)]
+        self._spec = {"t_max": t_max, "room": max_new_tokens + t_max, "slots": slots, "flip": 0, "t_prev": 0,
+                      "n_commit": torch.zeros(1, dtype=torch.int32, device=dev),
+                      "kidx": torch.arange(self.conv_kernel_size, device=dev), "tidx": torch.arange(t_max, device=dev),
+                      "base": {i: self._kv_len[i] for i in self.attention_layers},
+                      # host side: tokens kept of the forwards before the last one / of the last one — upper bounds, and
+                      # flagged as such, while a device-side commit has not been reported (note_committed)
+                      "done": 0, "exact": True, "last_k": 0, "last_exact": True,
+                      "flush": {}, "cidx": None, "rows": {}, "lens_t": {}}
+        self.speculating = True
+
+    def _spec_views(self, layer_idx, which, T):
+        """Operand views of T tokens in a layer's slot: which = 0 the one this forward writes, 1 the previous forward's."""
+        d_in, G, N, H = self._mamba_dims
+        B = self.ssm_states[layer_idx].shape[0]
+        sl = self._spec["slots"][layer_idx][self._spec["flip"] ^ which]
+        W = d_in + 2 * G * N + H
+        return (sl["x"][:B * T * d_in].view(B, T, d_in), sl["B"][:B * G * T * N].view(B, G, T, N),
+                sl["C"][:B * G * T * N].view(B, G, T, N), sl["tail"][:B * T * W].view(B, T, W))
+
+    def spec_prev_operands(self, layer_idx):
+        """(x, dt, B, C) of the previous forward as the recurrence kernels take them, or None before the first one."""
+        T = self._spec["t_prev"]
+        if T == 0:
+            return None
+        d_in, G, N, H = self._mamba_dims
+        x, Bm, Cm, tail = self._spec_views(layer_idx, 1, T)
+        return (x.view(x.shape[0], T, H, d_in // H), tail[..., d_in + 2 * G * N:], Bm.transpose(1, 2), Cm.transpose(1, 2))
+
+    # host bookkeeping of a provisional forward, in ONE place: the eager forward runs it beside its device work, a replayed
+    # graph (GraphedSpecStep) runs it alone — the capture executed exactly these functions, so the two cannot drift apart
+    def spec_check(self, T: int):
+        """The host-side checks in front of a provisional forward of T tokens, eager or replayed."""
+        sp = self._spec
+        if T > sp["t_max"]:
+            raise RuntimeError(f"speculation: {T} tokens in one forward, begin_speculation reserved t_max = {sp['t_max']}")
+        if sp["done"] + sp["last_k"] + T > sp["room"]:
+            raise RuntimeError("speculation: the key / value rows reserved by begin_speculation are used up")
+
+    def _spec_host_end(self, T: int):
+        sp = self._spec
+        sp["done"] += sp["last_k"]
+        sp["exact"] = sp["exact"] and sp["last_exact"]
+        sp["flip"] ^= 1
+        sp["t_prev"], sp["last_k"], sp["last_exact"] = int(T), 0, True
+
+    def _spec_host_commit(self, k):
+        """k: the host value, or None for a device-side commit nobody has reported yet (upper bound: every token)."""
+        sp = self._spec
+        sp["last_k"], sp["last_exact"] = (sp["t_prev"], False) if k is None else (int(k), True)
+
+    def spec_replayed(self, T: int):
+        """Host side of a REPLAYED step (forward + device-side commit), behind `spec_check(T)` in front of the launch: what
+        the captured functions did on the host."""
+        self._spec_host_end(T)
+        self._spec_host_commit(None)
+
+    def spec_begin_forward(self, T: int):
+        """Host checks and the device-side indices of one provisional forward (no host sync)."""
+        self.spec_check(T)
+        sp = self._spec
+        sp["cidx"] = sp["kidx"] + sp["n_commit"]
+        sp["rows"] = {n: pos + sp["tidx"][:T] for n, (pos, _) in self._static.items()}
+        sp["lens_t"] = {n: lens + T for n, (_, lens) in self._static.items()}
+
+    def spec_commit_conv(self, layer_idx):
+        """conv state <- the last K columns of [state | the previous forward's pre-conv rows[:n_commit]]: a gather with a
+        device index (nothing to do before the first forward)."""
+        T = self._spec["t_prev"]
+        if T == 0:
+            return
+        cs = self.conv_states[layer_idx]
+        d_in, G, N, H = self._mamba_dims
+        pre = self._spec_views(layer_idx, 1, T)[3][..., :d_in + 2 * G * N]
+        cs.copy_(torch.cat([cs, pre.transpose(1, 2).to(cs.dtype)], dim=-1).index_select(-1, self._spec["cidx"]))
+
+    def spec_end_forward(self, T: int):
+        """The forward's tokens are now the provisional ones: none of them kept until `commit` says so."""
+        self._spec_host_end(T)
+        self._spec["n_commit"].zero_()
+
+    def commit(self, k):
+        """Keep the first k tokens of the last forward: an int, or a tensor on the cache's device (no host sync; the caller
+        reports the value with `note_committed` once it has read it).  May be called again with a smaller k before the
+        next forward."""
+        if not self.speculating:
+            raise RuntimeError("commit: the cache is not in speculation mode")
+        sp = self._spec
+        T = sp["t_prev"]
+        if isinstance(k, torch.Tensor):
+            kt = k.reshape(1).to(torch.int32).clamp(0, T)
+            self._spec_host_commit(None)
+        else:
+            if not 0 <= int(k) <= T:
+                raise ValueError(f"commit: k = {k} outside [0, {T}] (the tokens of the last forward)")
+            kt = torch.full((1,), int(k), dtype=torch.int32, device=sp["n_commit"].device)
+            self._spec_host_commit(k)
+        delta = kt - sp["n_commit"]
+        for pos, lens in self._static.values():
+            pos += delta
+            lens += delta
+        sp["n_commit"].copy_(kt)
+
+    def note_committed(self, k: int):
+        """Host side of a device-side `commit(tensor)`: the value, once the caller has read it back."""
+        if not 0 <= int(k) <= self._spec["t_prev"]:
+            raise ValueError("note_committed: k outside the last forward")
+        self._spec_host_commit(k)
+
+    def end_speculation(self):
+        """Fold the kept tokens of the last forward in (one flush launch per Mamba layer, the conv state), fix the K / V
+        views to the committed length and free the slots: the cache is then what plain steps over the kept tokens leave."""
+        if not self.speculating:
+            return
+        sp = self._spec
+        if sp["t_prev"] > 0:
+            sp["cidx"] = sp["kidx"] + sp["n_commit"]
+            for i, fl in sp["flush"].items():
+                self.spec_commit_conv(i)
+                K.selective_state_update_spec(self.ssm_states[i], self.spec_prev_operands(i), sp["n_commit"], None,
+                                              fl["A"], dt_bias=fl["dt_bias"], dt_softplus=True, dt_limit=fl["dt_limit"],
+                                              group_map=fl["group_map"])
+        first = self.attention_layers[0]
+        if sp["exact"] and sp["last_exact"]:
+            done = sp["done"] + sp["last_k"]
+        else:       # a device-side commit nobody reported: one read
+            done = int(self._static_of[first][0]) - sp["base"][first]
+        for i in self.attention_layers:
+            n = sp["base"][i] + done
+            kb, vb = self._kv_buf[i]
+            self._kv_len[i] = n
+            self.key_cache[i], self.value_cache[i] = kb[:, :n], vb[:, :n]
+        self._static, self._static_of = {}, {}
+        self.speculating, self._spec = False, None
 
     def update_conv_state(self, layer_idx, new_conv_state, cache_init=False):
         assert cache_init
@@ -430,6 +602,8 @@ class NemotronHMamba2Mixer(nn.Module):
         gate, xBC, dt = projected_states.split([d_in, self.conv_dim, self.num_heads], dim=-1)
         w = self.conv1d.weight.squeeze(1)
         negA, D32, dtb32 = self._consts()
+        if decode and getattr(cache_params, "speculating", False):
+            return self._speculate(cache_params, gate, projected_states, w, negA, D32, dtb32)
         if decode and seq_len > 1:
             return self._continue(cache_params, gate, xBC, dt, w, negA, D32, dtb32)
         if decode:
@@ -500,6 +674,30 @@ class NemotronHMamba2Mixer(nn.Module):
             y = K.selective_state_update_seq(cache_params.ssm_states[idx], x, dt, negA, Bm, Cm, D=D32, dt_bias=dtb32,
                                              dt_softplus=True, dt_limit=self.time_step_limit, group_map=self.group_map)
         CONTINUE_LAST_PATH = "scan" if scan else "seq"
+        y = self.norm(y.reshape(batch_size, seq_len, d_in), gate)
+        return self.out_proj(y)
+
+    def _speculate(self, cache_params, gate, projected_states, w, negA, D32, dtb32):
+        """T >= 1 provisional tokens (cache.begin_speculation): the cache's conv / SSM states advance by the tokens KEPT
+        of the previous forward only — the conv state by a gather, the SSM state inside the commit phase of
+        tv_selective_state_update_spec — and this forward's tokens are computed from there without being stored.  Their
+        operands stay in the cache's slot for the next forward's commit phase."""
+        batch_size, seq_len, _ = projected_states.shape
+        d_in, idx = self.intermediate_size, self.layer_idx
+        sp = cache_params._spec
+        cache_params.spec_commit_conv(idx)
+        conv_state = cache_params.conv_states[idx]
+        halo = conv_state[..., 1:].transpose(1, 2)                       # (B, K-1, C)
+        prev = cache_params.spec_prev_operands(idx)
+        xs, Bs, Cs, tail = cache_params._spec_views(idx, 0, seq_len)
+        tail.copy_(projected_states[..., d_in:])                         # the pre-conv rows | dt, at a fixed address
+        x, Bm, Cm = K.causal_conv1d_xbc_into(tail[..., :self.conv_dim], w, self.conv1d.bias, d_in, self.n_groups,
+                                             self.ssm_state_size, (xs, Bs, Cs), activation=self.activation, halo=halo)
+        new = (x.view(batch_size, seq_len, -1, self.head_dim), tail[..., self.conv_dim:], Bm, Cm)
+        sp["flush"][idx] = {"A": negA, "dt_bias": dtb32, "dt_limit": self.time_step_limit, "group_map": self.group_map}
+        y = K.selective_state_update_spec(cache_params.ssm_states[idx], prev, sp["n_commit"], new, negA, D=D32,
+                                          dt_bias=dtb32, dt_softplus=True, dt_limit=self.time_step_limit,
+                                          group_map=self.group_map)
         y = self.norm(y.reshape(batch_size, seq_len, d_in), gate)
         return self.out_proj(y)
 
@@ -590,6 +788,17 @@ class NemotronHAttention(nn.Module):
         q = _linear(self.q_proj, hidden_states).view(bsz, q_len, self.num_heads, self.head_dim)
         k = _linear(self.k_proj, hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
         v = _linear(self.v_proj, hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
+        if getattr(past_key_value, "speculating", False) and is_continuation(past_key_value, cache_position):
+            # provisional rows behind the committed ones (rejected rows are overwritten by the next step); the key count
+            # comes from the device
+            kb, vb = past_key_value.kv_buffers(self.layer_idx)
+            n = past_key_value._spec["base"][self.layer_idx]
+            rows = past_key_value._spec["rows"][n]
+            kb.index_copy_(1, rows, k)
+            vb.index_copy_(1, rows, v)
+            o = K.flash_attn_append(q, kb, vb, seqlens_k=past_key_value._spec["lens_t"][n])
+            o = _linear(self.o_proj, o.reshape(bsz, q_len, self.num_heads * self.head_dim))
+            return o, None, past_key_value
         if past_key_value is not None:
             k, v = past_key_value.update(k, v, self.layer_idx)
         if past_key_value is not None and q_len == 1 and past_key_value.static_decode:
@@ -834,7 +1043,15 @@ class NemotronHModel(PdropMixin, nn.Module):
         if continuation and hidden.shape[1] > 1 and getattr(past_key_values, "static_decode", False):
             raise RuntimeError("continuation: the cache is in static-decode mode (fixed buffers, one token per step); "
                                "call cache.end_static_decode() before appending several tokens")
-        fused_step = (_fused_decode(hidden) and past_key_values is not None and cache_position is not None
+        speculating = continuation and getattr(past_key_values, "speculating", False)
+        if getattr(past_key_values, "speculating", False) and not continuation:
+            raise RuntimeError("speculation: the cache takes continuations only (cache_position > 0)")
+        if speculating:
+            if hidden.shape[1] > continue_t_seq():
+                raise RuntimeError(f"speculation: {hidden.shape[1]} tokens in one forward, more than continue_t_seq() = "
+                                   f"{continue_t_seq()} (the range of the in-register recurrence)")
+            past_key_values.spec_begin_forward(hidden.shape[1])
+        fused_step = (_fused_decode(hidden) and not speculating and past_key_values is not None and cache_position is not None
                       and int(cache_position[0]) > 0 and not output_hidden_states and not self.check_nan
                       and hidden.shape[-1] % 8 == 0 and hidden.shape[-1] <= 8192
                       and self._all_matrices_bf16())
@@ -875,6 +1092,8 @@ class NemotronHModel(PdropMixin, nn.Module):
                 normed, hidden = block.norm(hidden, residual=delta, return_sum=True)
             delta = block.mix(normed, past_key_values, cache_position, None, position_ids)
         hidden = self.norm_f(hidden, residual=delta) if delta is not None else self.norm_f(hidden)
+        if speculating:
+            past_key_values.spec_end_forward(hidden.shape[1])
         if output_hidden_states:
             all_hidden += (hidden,)
         return BaseModelOutputWithPastAndLabels(

@@ -7,6 +7,7 @@ import math
 import pytest
 import torch
 
+from attn_accuracy import assert_rows_close
 from conftest import golden_state_dict, load_golden
 from oracle import ops as R
 
@@ -125,9 +126,11 @@ def _append_case(K, B, T, Lk, Hq, Hkv, seed):
     assert K.flash_attn_append_calls() == calls + 1, "fell back to the prefill kernel"
     assert torch.isfinite(o.float()).all() and torch.isfinite(lse).all()
     close(o, o_ref, 2e-2, 1e-2, "o")
+    assert_rows_close(o, o_ref, torch.bfloat16, f"append B {B} T {T} Lk {Lk} H {Hq}/{Hkv}")
     close(lse, lse_ref, 1e-3, 2e-3, "lse")
     o2 = K.flash_attn_func(qd, kd, vd, causal=True)
     close(o, o2.float().cpu(), 2e-2, 1e-2, "against the prefill kernel")
+    assert_rows_close(o2, o_ref, torch.bfloat16, f"prefill kernel on the append case T {T} Lk {Lk} H {Hq}/{Hkv}")
 
 
 @pytest.mark.parametrize("B,T,Lk,Hq,Hkv", [
@@ -168,6 +171,7 @@ def test_flash_attn_append_device_lengths_and_strided_cache(K):
     for b, n in enumerate(lens):
         o_ref, lse_ref = R.attention_ref(q[b:b + 1].float().cpu(), k[b:b + 1, :n].float().cpu(), v[b:b + 1, :n].float().cpu(), True)
         close(o[b:b + 1], o_ref, 2e-2, 1e-2, f"o[{b}]")
+        assert_rows_close(o[b:b + 1], o_ref, torch.bfloat16, f"append device length {n}")
         close(lse[b:b + 1], lse_ref, 1e-3, 2e-3, f"lse[{b}]")
     with pytest.raises(K.TimeViperHipError):
         K.flash_attn_append(q, k, v, seqlens_k=sl.to(torch.int64))

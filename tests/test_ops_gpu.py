@@ -8,6 +8,7 @@ import pytest
 from pathlib import Path
 import torch
 
+from attn_accuracy import assert_rows_close
 from conftest import golden_state_dict, load_golden
 from oracle import ops as R
 
@@ -552,6 +553,7 @@ def test_flash_attention(K, dtype, B, Lq, Lk, Hq, Hkv, D, causal):
     o, lse = K.flash_attn_func(q.to(DEV), k.to(DEV), v.to(DEV), causal=causal, return_lse=True)
     rt, at = (2e-2, 1e-2) if dtype == torch.bfloat16 else (4e-3, 2e-3)
     close(o, o_ref, rt, at, "o")
+    assert_rows_close(o, o_ref, dtype, f"prefill {Lq}x{Lk} H {Hq}/{Hkv} d {D} causal {causal}")
     close(lse, lse_ref, 1e-3, 2e-3, "lse")
 
 
@@ -578,6 +580,7 @@ def test_flash_attention_streaming(K, dtype, B, Lq, Lk, Hq, Hkv, D):
     o, lse = K.flash_attn_func(q, k, v, causal=False, return_lse=True)
     rt, at = (2e-2, 1e-2) if dtype == torch.bfloat16 else (4e-3, 2e-3)
     close(o, o_ref, rt, at, "o")
+    assert_rows_close(o, o_ref, dtype, f"ViT auto {B}x{Lq}x{Lk} H {Hq}/{Hkv} d {D}")
     close(lse, lse_ref, 1e-3, 2e-3, "lse")
     o2 = K.flash_attn_func(q, k, v, causal=False)                  # same bits on a second call (no stale ring state)
     assert torch.equal(o, o2)
@@ -617,6 +620,8 @@ def test_flash_attention_streaming_row_sums_on_the_matrix_pipe(K, dtype, B, Lq, 
     e1 = (o1.float().cpu() - o_ref).norm() / o_ref.norm()
     e0 = (o0.float().cpu() - o_ref).norm() / o_ref.norm()
     assert e1 < 1.05 * e0 + 1e-5, (e1.item(), e0.item())           # and is no further from the fp32 oracle
+    assert_rows_close(o1, o_ref, dtype, f"ViT variant 5 {B}x{Lq}x{Lk} H {Hq}/{Hkv} d {D}")         # ... row by row, each
+    assert_rows_close(o0, o_ref, dtype, f"ViT variant 3 {B}x{Lq}x{Lk} H {Hq}/{Hkv} d {D}")
 
 
 @pytest.mark.parametrize("B,Lq,Lk,Hq,Hkv,D,sharp", [
@@ -654,6 +659,8 @@ def test_flash_attention_generated_tile_loop(K, B, Lq, Lk, Hq, Hkv, D, sharp):
     e1 = (o1.float().cpu() - o_ref).norm() / o_ref.norm()
     e0 = (o0.float().cpu() - o_ref).norm() / o_ref.norm()
     assert e1 < 1.15 * e0 + 1e-5, (e1.item(), e0.item())
+    assert_rows_close(o1, o_ref, torch.bfloat16, f"ViT variant 4 {B}x{Lq}x{Lk} H {Hq}/{Hkv} d {D} sharp {sharp}")
+    assert_rows_close(o0, o_ref, torch.bfloat16, f"ViT variant 5 {B}x{Lq}x{Lk} H {Hq}/{Hkv} d {D} sharp {sharp}")
 
 
 def test_flash_attention_spiked_max(K):
@@ -669,6 +676,7 @@ def test_flash_attention_spiked_max(K):
     o_ref, _ = R.attention_ref(q.float(), k.float(), v.float(), True)
     o = K.flash_attn_func(q.to(DEV), k.to(DEV), v.to(DEV), causal=True)
     close(o, o_ref, 2e-2, 1e-2)
+    assert_rows_close(o, o_ref, torch.bfloat16, "prefill spiked max")
 
 
 # ---------------------------------------------------------------- decode-step linears
@@ -784,6 +792,7 @@ def test_flash_attn_decode_split_kv(K, B, Lk, Hq, Hkv):
     qd, kd, vd = q.to(DEV), k.to(DEV), v.to(DEV)
     o, lse = K.flash_attn_decode(qd, kd, vd, return_lse=True)
     close(o, o_ref, 2e-2, 1e-2, "o")
+    assert_rows_close(o, o_ref, torch.bfloat16, f"decode B {B} Lk {Lk} H {Hq}/{Hkv}")
     close(lse, lse_ref, 1e-3, 2e-3, "lse")
     # flash_attn_func routes one-query calls here; TV_ATTN_DECODE=0 keeps them on the prefill kernel
     o2 = K.flash_attn_func(qd, kd, vd, causal=True)
@@ -794,6 +803,7 @@ def test_flash_attn_decode_split_kv(K, B, Lk, Hq, Hkv):
     finally:
         del os.environ["TV_ATTN_DECODE"]
     close(o, o3.float().cpu(), 2e-2, 1e-2, "against the prefill kernel")
+    assert_rows_close(o3, o_ref, torch.bfloat16, f"prefill kernel, one query row, Lk {Lk} H {Hq}/{Hkv}")
 
 
 def test_flash_attn_decode_device_lengths_and_strided_cache(K):
@@ -815,12 +825,14 @@ def test_flash_attn_decode_device_lengths_and_strided_cache(K):
     for b, n in enumerate(lens):
         o_ref, lse_ref = R.attention_ref(q[b:b + 1].float().cpu(), k[b:b + 1, :n].float().cpu(), v[b:b + 1, :n].float().cpu(), True)
         close(o[b:b + 1], o_ref, 2e-2, 1e-2, f"o[{b}]")
+        assert_rows_close(o[b:b + 1], o_ref, torch.bfloat16, f"decode device length {n}")
         close(lse[b:b + 1], lse_ref, 1e-3, 2e-3, f"lse[{b}]")
     # a growing cache under ONE set of launch parameters: the length is read on the device
     sl.fill_(10)
     o10 = K.flash_attn_decode(q, k, v, seqlens_k=sl)
     o_ref, _ = R.attention_ref(q[0:1].float().cpu(), k[0:1, :10].float().cpu(), v[0:1, :10].float().cpu(), True)
     close(o10[0:1], o_ref, 2e-2, 1e-2, "length 10")
+    assert_rows_close(o10[0:1], o_ref, torch.bfloat16, "decode device length 10")
     with pytest.raises(K.TimeViperHipError):
         K.flash_attn_decode(q, k, v, seqlens_k=sl.to(torch.int64))
 
@@ -838,6 +850,7 @@ def test_flash_attn_decode_spiked_max(K):
     o_ref, lse_ref = R.attention_ref(q.float(), k.float(), v.float(), True)
     o, lse = K.flash_attn_decode(q.to(DEV), k.to(DEV), v.to(DEV), return_lse=True)
     close(o, o_ref, 2e-2, 1e-2, "o")
+    assert_rows_close(o, o_ref, torch.bfloat16, "decode spiked max")
     close(lse, lse_ref, 1e-3, 2e-3, "lse")
 
 
@@ -863,10 +876,12 @@ def test_sdpa_and_varlen_wrappers(K):
     o_ref, _ = R.attention_ref(q.float().transpose(1, 2), k.float().transpose(1, 2), v.float().transpose(1, 2), False)
     o = K.scaled_dot_product_attention(q.to(DEV), k.to(DEV), v.to(DEV))
     close(o.transpose(1, 2), o_ref, 2e-2, 1e-2)
+    assert_rows_close(o.transpose(1, 2), o_ref, torch.bfloat16, "sdpa wrapper")
     qkv = torch.stack([q, k, v], dim=0).permute(1, 3, 0, 2, 4).reshape(2 * 33, 3, 4, 64).contiguous()
     cu = torch.tensor([0, 33, 66], dtype=torch.int32)
     o2 = K.flash_attn_varlen_qkvpacked_func(qkv.to(DEV), cu.to(DEV), 33)
     close(o2.view(2, 33, 4, 64), o_ref, 2e-2, 1e-2)
+    assert_rows_close(o2.view(2, 33, 4, 64), o_ref, torch.bfloat16, "varlen wrapper, equal lengths")
 
 
 # --------------------------------------------------------------- token ops
@@ -1381,6 +1396,7 @@ def test_flash_attn_varlen_ragged_and_key_padding_mask(K):
         x = qkv[int(cu[i]):int(cu[i + 1])].float()[None]
         ref, _ = R.attention_ref(x[:, :, 0], x[:, :, 1], x[:, :, 2], False)
         close(out[int(cu[i]):int(cu[i + 1])], ref[0], 2e-2, 1e-2, f"sequence {i}")
+        assert_rows_close(out[int(cu[i]):int(cu[i + 1])], ref[0], torch.bfloat16, f"varlen ragged, sequence {i} of {n}")
     # padded batch: (B, S) mask with holes in the middle and at the ends
     B, S = 3, 120
     mask = torch.rand(B, S, generator=g) > 0.3
@@ -1394,9 +1410,11 @@ def test_flash_attn_varlen_ragged_and_key_padding_mask(K):
         xb = x[b, keep].float()[None]
         ref, _ = R.attention_ref(xb[:, :, 0], xb[:, :, 1], xb[:, :, 2], False)
         close(o[b, keep], ref[0], 2e-2, 1e-2, f"batch {b}")
+        assert_rows_close(o[b, keep], ref[0], torch.bfloat16, f"key_padding_mask, batch {b}")
         assert float(o[b, ~mask[b]].abs().max()) == 0.0
     # already unpadded input through the module, causal
     o2, _ = FlashAttention()(qkv.to(DEV), cu_seqlens=cu.to(DEV), max_s=max(lens), causal=True)
     x0 = qkv[:257].float()[None]
     ref, _ = R.attention_ref(x0[:, :, 0], x0[:, :, 1], x0[:, :, 2], True)
     close(o2[:257], ref[0], 2e-2, 1e-2, "causal, first sequence")
+    assert_rows_close(o2[:257], ref[0], torch.bfloat16, "varlen causal, first sequence")

@@ -6,6 +6,7 @@ import random
 import pytest
 import torch
 
+from attn_accuracy import assert_rows_close
 from oracle import ops as R
 from test_ops_gpu import TOL, close, run_scan, scan_inputs
 
@@ -68,6 +69,7 @@ def test_attention_random_shapes(K):
         rt, at = (2e-2, 1e-2) if dtype == torch.bfloat16 else (4e-3, 2e-3)
         tag = f"#{it} B{B} Lq{Lq} Lk{Lk} Hq{Hq} Hkv{Hkv} D{D} causal={causal} {dtype}"
         close(o, o_ref, rt, at, "o " + tag)
+        assert_rows_close(o, o_ref, dtype, "random shape " + tag)
         close(lse, lse_ref, 1e-3, 2e-3, "lse " + tag)
 
 

@@ -427,6 +427,22 @@ int tv_gemv_bf16_fwd(const void* x, const void* W, const void* bias, void* y, in
                      int group_size, void* conv_state, const void* conv_weight, const void* conv_bias,
                      int conv_row0, int conv_channels, void* stream);
 
+/* The same product for the few-token forwards (a continuation or a speculative step of T tokens on one sequence:
+ * torch.nn.Linear at 2 <= q_len <= 16), with the weights streamed once and the products on the matrix pipe:
+ *   y[m][n] = sum_k f(x)[m][k] W[n][k] (+ bias[n]),   1 <= M <= 16, x / W / y bf16, fp32 accumulation, one rounding of y.
+ * The arguments are tv_gemv_bf16_fwd's without the conv epilogue; `prologue` takes the same values with the same
+ * rounding points (1: ALL M rows of s go to sum_out).  K is not bounded by on-chip memory (f(x) is staged in slices);
+ * prologue 1 takes rows of K <= 8192 channels, prologue 3 groups of group_size <= 2048.  K, ldw, x_stride (and the
+ * strides of delta / gate / sum_out) multiples of 8 and, for M > 1, at least K; the operands 16-byte aligned; y rows may be
+ * y_stride >= N apart.  sum_out must not overlap x or delta: one work-group writes it while all of them read x + delta.
+ * Deterministic (no atomics), no workspace, no host synchronisation: capturable in a graph after one call outside it.
+ * Nothing is read past row M - 1 of x / delta / gate or past row N - 1 of W. */
+int tv_linear_rows_bf16_fwd(const void* x, const void* W, const void* bias, void* y, int M, int N, int K,
+                            int64_t x_stride, int64_t ldw, int64_t y_stride, int prologue, const void* delta,
+                            int64_t delta_stride, void* sum_out, int64_t sum_stride, const void* norm_weight,
+                            int norm_weight_dtype, float eps, const void* gate, int64_t gate_stride,
+                            int group_size, void* stream);
+
 /* The decode step of the same operator: ONE query token per sequence against a K / V cache (q_len == 1 in
  * modeling_nano.py:1198-1209; cache layout of HybridMambaAttentionDynamicCache, :205-360).  q (B, Hq, D) and
  * o (B, Hq, D) by batch / head strides, k / v (B, Lk, Hkv, D) as in tv_flash_attn_fwd; lse (B, Hq) fp32 or NULL.

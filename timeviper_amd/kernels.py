@@ -762,6 +762,73 @@ def gemv_fused(x, weight, bias=None, prologue=GEMV_NONE, delta=None, sum_out=Non
     return y
 
 
+# (N, K) of a weight -> the row counts T at which the library GEMM measured faster than tv_linear_rows_bf16_fwd
+# (devtools/bench_speculative.py, profiles/rows_linear.json "stay_on_library"): those products stay on the library.
+ROWS_ON_LIBRARY: dict = {}
+
+
+def _rows_on_library(T: int, N: int, K: int) -> bool:
+    return T in ROWS_ON_LIBRARY.get((N, K), ())
+
+
+def linear_rows_takes(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Shapes tv_linear_rows_bf16_fwd is written for: the 1..16 token rows of ONE sequence, bf16 (1, T, K) or (T, K) with
+    dense rows, against a bf16 (N, K) weight."""
+    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[0] != 1):
+        return False
+    K = x.shape[-1]
+    return (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and weight.dim() == 2
+            and 1 <= x.shape[-2] <= 16 and K % 8 == 0 and K >= 8 and weight.shape[1] == K and x.stride(-1) == 1
+            and x.stride(-2) % 8 == 0 and weight.stride(1) == 1 and weight.stride(0) % 8 == 0
+            and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
+            and not _rows_on_library(x.shape[-2], weight.shape[0], K))
+
+
+def linear_rows_fused(x, weight, bias=None, prologue=GEMV_NONE, delta=None, sum_out=None, norm_weight=None, eps=0.0,
+                      gate=None, group_size=0, out=None):
+    """y = f(x) @ weight.T (+ bias) for 1..16 rows — the linear layers of a few-token forward (torch.nn.Linear at
+    2 <= q_len <= 16 on one sequence), the weights streamed once, with gemv_fused's prologues (GEMV_*) and their rounding
+    points; GEMV_RMSNORM writes every row of the sum to `sum_out`.  `out`: a bf16 (..., N) tensor to write, whose rows may
+    be further apart than N (a column window of a wider buffer)."""
+    _gpu(x, weight, bias, delta, sum_out, norm_weight, gate, out)
+    K = x.shape[-1]
+    x2 = _rows2d(x)
+    M, N = x2.shape[0], weight.shape[0]
+    if weight.dim() != 2 or weight.shape[1] != K:
+        raise TimeViperHipError(f"linear_rows_fused: weight {tuple(weight.shape)} against rows of {K}")
+    if (x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.stride(1) != 1 or weight.stride(0) % 8
+            or K % 8):
+        raise TimeViperHipError("linear_rows_fused: bf16 x and weight with dense rows of a multiple of 8 elements only "
+                                f"(x {x.dtype}, weight {weight.dtype}, strides {tuple(weight.stride())}, K {K})")
+    if out is None:
+        y = torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
+        y2 = y.view(-1, N)
+    else:
+        y = out
+        if y.dtype != x.dtype or y.shape[-1] != N or y.numel() != M * N or y.stride(-1) != 1:
+            raise TimeViperHipError(f"linear_rows_fused: out {tuple(y.shape)} {y.dtype} is not {M} bf16 rows of {N}")
+        y2 = y if y.dim() == 2 else y.view(-1, N)     # (a view, or an error: never a copy)
+    d2 = None if delta is None else _rows2d(delta)
+    g2 = None if gate is None else _rows2d(gate)
+    s2 = None if sum_out is None else (sum_out if sum_out.dim() == 2 else sum_out.view(-1, K))
+    for t in (d2, g2, s2):
+        if t is not None and (t.shape != x2.shape or t.dtype != x.dtype or t.stride(1) != 1):
+            raise TimeViperHipError("linear_rows_fused: delta / gate / sum_out must have x's shape and dtype")
+    if bias is not None and (bias.dtype != x.dtype or not bias.is_contiguous() or bias.numel() != N):
+        raise TimeViperHipError("linear_rows_fused: bias must be N contiguous entries of x's dtype")
+    nw_dt = 0
+    if norm_weight is not None:
+        if not norm_weight.is_contiguous() or norm_weight.numel() != K:
+            raise TimeViperHipError("linear_rows_fused: norm_weight must be a contiguous vector of K entries")
+        nw_dt = _dt(norm_weight)
+    check(_capi.lib().tv_linear_rows_bf16_fwd(
+        _p(x2), _p(weight), _p(bias), _p(y2), M, N, K, x2.stride(0), weight.stride(0), y2.stride(0), int(prologue),
+        _p(d2), 0 if d2 is None else d2.stride(0), _p(s2), 0 if s2 is None else s2.stride(0),
+        _p(norm_weight), nw_dt, float(eps), _p(g2), 0 if g2 is None else g2.stride(0), int(group_size),
+        _stream()), "tv_linear_rows_bf16_fwd")
+    return y
+
+
 def _decode_attn_takes(q, k, v) -> bool:
     """Shapes tv_attn_decode_fwd is written for (the rest stays on tv_flash_attn_fwd with one query row)."""
     return (q.dtype == torch.bfloat16 and q.shape[-1] == 128 and k.shape[1] >= 256

@@ -488,6 +488,18 @@ def _fused_decode(x: torch.Tensor) -> bool:
             and not torch.is_grad_enabled() and os.environ.get("TV_DECODE_FUSED", "1") != "0")
 
 
+ROWS_FUSED_DEFAULT = "0"       # what TV_ROWS_FUSED is taken to be when it is not set
+
+
+def _fused_rows(x: torch.Tensor) -> bool:
+    """The linear layers of a few-token forward on one sequence (2..16 rows: a continuation, a speculative step) run on
+    tv_linear_rows_bf16_fwd with the operator in front of them in the prologue under TV_ROWS_FUSED=1; without it (the
+    default until the step is measured faster on an MI355X) torch.nn.Linear + the stand-alone kernels
+    run (same arithmetic, library GEMM).  Read per call."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3 and x.shape[0] == 1 and 2 <= x.shape[1] <= 16
+            and not torch.is_grad_enabled() and os.environ.get("TV_ROWS_FUSED", ROWS_FUSED_DEFAULT) != "0")
+
+
 # a continuation (T > 1 tokens behind a prefill) of up to this many tokens updates the SSM state in place, token by token
 # inside one launch; longer ones run the chunked scan from the cached state.  Measured (devtools/bench_continue.py,
 # profiles/continue_kernels.json, 9B dims): the largest T at which the sequence kernel is still the fastest of {itself,
@@ -506,9 +518,11 @@ def is_continuation(past_key_values, cache_position) -> bool:
     return past_key_values is not None and cache_position is not None and int(cache_position[0]) > 0
 
 
-def _linear(mod: nn.Linear, x: torch.Tensor) -> torch.Tensor:
+def _linear(mod: nn.Linear, x: torch.Tensor, continuation: bool = False) -> torch.Tensor:
     if _fused_decode(x) and K.gemv_takes(x, mod.weight):
         return K.gemv_fused(x, mod.weight, mod.bias)
+    if continuation and _fused_rows(x) and K.linear_rows_takes(x, mod.weight):
+        return K.linear_rows_fused(x, mod.weight, mod.bias)
     return mod(x)
 
 
@@ -646,11 +660,11 @@ class NemotronHMamba2Mixer(nn.Module):
             return out, ssm_state, res[2]
         return out
 
-    def _continue(self, cache_params, gate, xBC, dt, w, negA, D32, dtb32):
+    def _continue(self, cache_params, gate, xBC, dt, w, negA, D32, dtb32, finish=True):
         """T > 1 tokens behind a prefill (or earlier continuations / decode steps): the conv starts from the cached
         pre-conv rows, the recurrence from the cached state.  Up to `continue_t_seq()` tokens the state stays where it
         is (tv_selective_state_update_seq: every row read and written once); longer runs take the chunked scan with
-        the cached state as its initial state."""
+        the cached state as its initial state.  `finish=False` returns y in front of the gated norm (rows_fused)."""
         global CONTINUE_LAST_PATH
         batch_size, seq_len, _ = xBC.shape
         d_in, Kw, idx = self.intermediate_size, self.conv_kernel_size, self.layer_idx
@@ -674,14 +688,17 @@ class NemotronHMamba2Mixer(nn.Module):
             y = K.selective_state_update_seq(cache_params.ssm_states[idx], x, dt, negA, Bm, Cm, D=D32, dt_bias=dtb32,
                                              dt_softplus=True, dt_limit=self.time_step_limit, group_map=self.group_map)
         CONTINUE_LAST_PATH = "scan" if scan else "seq"
-        y = self.norm(y.reshape(batch_size, seq_len, d_in), gate)
-        return self.out_proj(y)
+        y = y.reshape(batch_size, seq_len, d_in)
+        if not finish:
+            return y
+        return self.out_proj(self.norm(y, gate))
 
-    def _speculate(self, cache_params, gate, projected_states, w, negA, D32, dtb32):
+    def _speculate(self, cache_params, gate, projected_states, w, negA, D32, dtb32, finish=True):
         """T >= 1 provisional tokens (cache.begin_speculation): the cache's conv / SSM states advance by the tokens KEPT
         of the previous forward only — the conv state by a gather, the SSM state inside the commit phase of
         tv_selective_state_update_spec — and this forward's tokens are computed from there without being stored.  Their
-        operands stay in the cache's slot for the next forward's commit phase."""
+        operands stay in the cache's slot for the next forward's commit phase.  `finish=False` returns y in front of the
+        gated norm (rows_fused)."""
         batch_size, seq_len, _ = projected_states.shape
         d_in, idx = self.intermediate_size, self.layer_idx
         sp = cache_params._spec
@@ -698,8 +715,31 @@ class NemotronHMamba2Mixer(nn.Module):
         y = K.selective_state_update_spec(cache_params.ssm_states[idx], prev, sp["n_commit"], new, negA, D=D32,
                                           dt_bias=dtb32, dt_softplus=True, dt_limit=self.time_step_limit,
                                           group_map=self.group_map)
-        y = self.norm(y.reshape(batch_size, seq_len, d_in), gate)
-        return self.out_proj(y)
+        y = y.reshape(batch_size, seq_len, d_in)
+        if not finish:
+            return y
+        return self.out_proj(self.norm(y, gate))
+
+    def rows_fused(self, hidden, delta, norm, cache_params):
+        """A few tokens behind a prefill (`_fused_rows`), committed or provisional: the block's RMSNorm (+ residual add)
+        inside in_proj, `_continue` / `_speculate` up to the gated norm, the gated norm inside out_proj.  Returns
+        (residual stream, mixer output)."""
+        new_hidden = torch.empty_like(hidden) if delta is not None else hidden
+        d_in = self.intermediate_size
+        proj = K.linear_rows_fused(hidden, self.in_proj.weight, self.in_proj.bias, K.GEMV_RMSNORM, delta=delta,
+                                   sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
+                                   eps=norm.variance_epsilon)
+        gate, xBC, dt = proj.split([d_in, self.conv_dim, self.num_heads], dim=-1)
+        w = self.conv1d.weight.squeeze(1)
+        negA, D32, dtb32 = self._consts()
+        if getattr(cache_params, "speculating", False):
+            y = self._speculate(cache_params, gate, proj, w, negA, D32, dtb32, finish=False)
+        else:
+            y = self._continue(cache_params, gate, xBC, dt, w, negA, D32, dtb32, finish=False)
+        out = K.linear_rows_fused(y, self.out_proj.weight, self.out_proj.bias, K.GEMV_GATED,
+                                  norm_weight=self.norm.weight, eps=self.norm.variance_epsilon, gate=gate,
+                                  group_size=self.norm.group_size)
+        return new_hidden, out
 
     def decode_fused(self, hidden, delta, norm, cache_params):
         """One decode token with the block's RMSNorm (+ residual add) inside in_proj and the gated norm inside out_proj:
@@ -758,6 +798,14 @@ class NemotronHMLP(nn.Module):
                          eps=norm.variance_epsilon)
         return new_hidden, K.gemv_fused(u, self.down_proj.weight, self.down_proj.bias, K.GEMV_RELU2)
 
+    def rows_fused(self, hidden, delta, norm):
+        """A few tokens (`_fused_rows`): RMSNorm (+ residual add) inside up_proj, relu^2 inside down_proj — 2 launches."""
+        new_hidden = torch.empty_like(hidden) if delta is not None else hidden
+        u = K.linear_rows_fused(hidden, self.up_proj.weight, self.up_proj.bias, K.GEMV_RMSNORM, delta=delta,
+                                sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
+                                eps=norm.variance_epsilon)
+        return new_hidden, K.linear_rows_fused(u, self.down_proj.weight, self.down_proj.bias, K.GEMV_RELU2)
+
 
 class NemotronHAttention(nn.Module):
     """Causal GQA attention without positional encoding (reference :1012-1220)."""
@@ -785,19 +833,13 @@ class NemotronHAttention(nn.Module):
             raise NotImplementedError("padding masks are not on the inference path (mask is None "
                                       "under flash_attention_2, reference :2208-2213)")
         bsz, q_len, _ = hidden_states.size()
-        q = _linear(self.q_proj, hidden_states).view(bsz, q_len, self.num_heads, self.head_dim)
-        k = _linear(self.k_proj, hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
-        v = _linear(self.v_proj, hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
-        if getattr(past_key_value, "speculating", False) and is_continuation(past_key_value, cache_position):
-            # provisional rows behind the committed ones (rejected rows are overwritten by the next step); the key count
-            # comes from the device
-            kb, vb = past_key_value.kv_buffers(self.layer_idx)
-            n = past_key_value._spec["base"][self.layer_idx]
-            rows = past_key_value._spec["rows"][n]
-            kb.index_copy_(1, rows, k)
-            vb.index_copy_(1, rows, v)
-            o = K.flash_attn_append(q, kb, vb, seqlens_k=past_key_value._spec["lens_t"][n])
-            o = _linear(self.o_proj, o.reshape(bsz, q_len, self.num_heads * self.head_dim))
+        cont = is_continuation(past_key_value, cache_position)
+        q = _linear(self.q_proj, hidden_states, cont).view(bsz, q_len, self.num_heads, self.head_dim)
+        k = _linear(self.k_proj, hidden_states, cont).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
+        v = _linear(self.v_proj, hidden_states, cont).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
+        if getattr(past_key_value, "speculating", False) and cont:
+            o = self._attend_provisional(q, k, v, past_key_value)
+            o = _linear(self.o_proj, o.reshape(bsz, q_len, self.num_heads * self.head_dim), True)
             return o, None, past_key_value
         if past_key_value is not None:
             k, v = past_key_value.update(k, v, self.layer_idx)
@@ -811,9 +853,18 @@ class NemotronHAttention(nn.Module):
         else:
             o = K._flash_attention_forward(q, k, v, attention_mask=None, query_length=q_len,
                                            is_causal=self.is_causal)
-        o = _linear(self.o_proj, o.reshape(bsz, q_len, self.num_heads * self.head_dim))
+        o = _linear(self.o_proj, o.reshape(bsz, q_len, self.num_heads * self.head_dim), cont)
         return o, None, past_key_value
 
+    def _attend_provisional(self, q, k, v, cache):
+        """The attention of a speculative step: the T rows go behind the committed ones (rejected rows are overwritten by
+        the next step), the key count comes from the device."""
+        kb, vb = cache.kv_buffers(self.layer_idx)
+        n = cache._spec["base"][self.layer_idx]
+        rows = cache._spec["rows"][n]
+        kb.index_copy_(1, rows, k)
+        vb.index_copy_(1, rows, v)
+        return K.flash_attn_append(q, kb, vb, seqlens_k=cache._spec["lens_t"][n])
 
     def _qkv_weight(self):
         """[q; k; v] as one (N, K) matrix for the decode token's single product (a copy: 64 MB per layer at 9B dims), rebuilt
@@ -845,6 +896,26 @@ class NemotronHAttention(nn.Module):
         else:
             o = K._flash_attention_forward(q, kc, vc, attention_mask=None, query_length=1, is_causal=self.is_causal)
         return new_hidden, _linear(self.o_proj, o.reshape(B, 1, nq))
+
+    def rows_fused(self, hidden, delta, norm, cache):
+        """A few tokens behind a prefill (`_fused_rows`), committed or provisional: the block's RMSNorm (+ residual add) in
+        the prologue of ONE q / k / v product, the cache writes, split-KV attention, o_proj."""
+        B, T = hidden.shape[:2]
+        new_hidden = torch.empty_like(hidden) if delta is not None else hidden
+        nq, nkv = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
+        qkv = K.linear_rows_fused(hidden, self._qkv_weight(), None, K.GEMV_RMSNORM, delta=delta,
+                                  sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
+                                  eps=norm.variance_epsilon)
+        q, k, v = qkv.split([nq, nkv, nkv], dim=-1)
+        q = q.view(B, T, self.num_heads, self.head_dim)
+        k = k.view(B, T, self.num_key_value_heads, self.head_dim)
+        v = v.view(B, T, self.num_key_value_heads, self.head_dim)
+        if getattr(cache, "speculating", False):
+            o = self._attend_provisional(q, k, v, cache)
+        else:
+            kc, vc = cache.update(k, v, self.layer_idx)
+            o = K.flash_attn_append(q, kc, vc)
+        return new_hidden, K.linear_rows_fused(o.reshape(B, T, nq), self.o_proj.weight, None, K.GEMV_NONE)
 
 
 NemotronHFlashAttention2 = NemotronHAttention
@@ -1055,8 +1126,11 @@ class NemotronHModel(PdropMixin, nn.Module):
                       and int(cache_position[0]) > 0 and not output_hidden_states and not self.check_nan
                       and hidden.shape[-1] % 8 == 0 and hidden.shape[-1] <= 8192
                       and self._all_matrices_bf16())
+        # the same route for the 2..16 tokens of a continuation or a speculative step (tv_linear_rows_bf16_fwd)
+        rows_step = (_fused_rows(hidden) and continuation and not output_hidden_states and not self.check_nan
+                     and hidden.shape[-1] % 8 == 0 and hidden.shape[-1] <= 8192 and self._all_matrices_bf16())
         # attention blocks join when their projections carry no bias (the stacked q / k / v product takes none)
-        attn_fused = fused_step and not self.config.attention_bias
+        attn_fused = (fused_step or rows_step) and not self.config.attention_bias
         for layer_idx, block in enumerate(self.layers):
             if self.use_pdrop and train_pdrop_args is not None \
                     and layer_idx in self.pdrop_layers \
@@ -1085,6 +1159,12 @@ class NemotronHModel(PdropMixin, nn.Module):
                     hidden, delta = block.mixer.decode_fused(hidden, delta, block.norm)
                 else:
                     hidden, delta = block.mixer.decode_fused(hidden, delta, block.norm, past_key_values)
+                continue
+            if rows_step and (block.block_type != "attention" or attn_fused):
+                if block.block_type == "mlp":
+                    hidden, delta = block.mixer.rows_fused(hidden, delta, block.norm)
+                else:
+                    hidden, delta = block.mixer.rows_fused(hidden, delta, block.norm, past_key_values)
                 continue
             if delta is None:
                 normed = block.norm(hidden)
@@ -1173,6 +1253,7 @@ class NemotronHForCausalLM(nn.Module):
         keep = self.config.num_logits_to_keep if logits_to_keep is None else logits_to_keep
         if isinstance(keep, int) and keep > 0:
             hidden = hidden[:, -keep:]
-        logits = _linear(self.lm_head, hidden.to(self.lm_head.weight.dtype)).float()
+        logits = _linear(self.lm_head, hidden.to(self.lm_head.weight.dtype),
+                         is_continuation(past_key_values, cache_position)).float()
         return CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=out.past_key_values,
                                       hidden_states=out.hidden_states)

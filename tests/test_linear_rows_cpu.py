@@ -1,5 +1,6 @@
 """CPU-side checks of tv_linear_rows_bf16_fwd (the few-token linear layers): the symbol, its binding, its argument checks
-(made before any HIP call, so they need no device), the wrapper's shape predicate, and the code objects' scratch use."""
+(made before any HIP call, so they need no device; tv_gemv_bf16_fwd makes them by the same code, csrc/linear_prologue.hpp,
+and is asked the same way), the wrapper's shape predicate, and the code objects' scratch use."""
 import re
 import shutil
 import subprocess
@@ -58,6 +59,60 @@ def test_argument_errors_are_returned_without_a_device(kw, status):
     lib = _capi.lib()
     assert call(lib, **kw) == status, (kw, lib.tv_last_error())
     assert b"linear_rows" in lib.tv_last_error()
+
+
+def call_gemv(lib, M=2, N=32, K=64, xs=None, ldw=None, ys=None, pro=0, nw=None, nw_dt=F32, group=0, x=P, W=P, y=P, delta=None,
+              sum_out=None):
+    return lib.tv_gemv_bf16_fwd(x, W, None, y, M, N, K, K if xs is None else xs, K if ldw is None else ldw,
+                                N if ys is None else ys, pro, delta, K, sum_out, K, nw, nw_dt, 1e-5, None, 0, group,
+                                None, None, None, 0, 0, None)
+
+
+@pytest.mark.parametrize("kw,status", [
+    (dict(M=0), -1),
+    (dict(M=5), -1),
+    (dict(K=12), -2),
+    (dict(pro=1), -1),                       # rmsnorm prologue without a norm weight
+    (dict(pro=3, group=32), -1),             # gated prologue without a norm weight
+    (dict(pro=3, nw=P, group=24), -1),       # 24 does not divide 64
+    (dict(x=None), -1),
+    (dict(x=P + 2), -2),                     # misaligned x
+    (dict(ldw=68), -2),
+    (dict(pro=1, nw=P, K=8200), -2),         # rmsnorm rows of <= 8192 channels
+    (dict(M=4, K=16392, N=8), -2),           # f(x) past the 128 KiB of LDS
+    (dict(pro=7), -1),
+    # the checks the two kernels share since linear_prologue.hpp: overlapping rows, the sum written over an operand
+    (dict(xs=32), -1),
+    (dict(ys=16), -1),
+    (dict(ldw=32), -1),
+    (dict(pro=1, nw=P, sum_out=P), -1),      # sum_out == x
+    (dict(pro=1, nw=P, delta=2 * P, sum_out=2 * P), -1),
+])
+def test_gemv_argument_errors_are_returned_without_a_device(kw, status):
+    """tv_gemv_bf16_fwd makes the same checks, by the same code, in front of any HIP call"""
+    from timeviper_amd import _capi
+    lib = _capi.lib()
+    assert call_gemv(lib, **kw) == status, (kw, lib.tv_last_error())
+    assert lib.tv_last_error().startswith(b"gemv:")
+
+
+def test_copies_of_strided_operands_outlive_the_helper(monkeypatch):
+    """A delta / gate whose inner stride is not 1 is copied to dense rows: the pointers handed to the C call must belong to
+    tensors the wrapper still holds when it launches (a freed copy's block may be handed to the output)."""
+    from timeviper_amd import kernels as K
+    monkeypatch.setattr(K, "_gpu", lambda *ts: None)
+    x = torch.zeros(1, 3, 64, dtype=torch.bfloat16)
+    W = torch.zeros(32, 64, dtype=torch.bfloat16)
+    wide = torch.ones(1, 3, 128, dtype=torch.bfloat16)
+    for kw in (dict(delta=wide[..., ::2], sum_out=torch.empty_like(x), gate=None), dict(delta=None, sum_out=None, gate=wide[..., ::2])):
+        x2, args, held = K._linear_operands("t", x, W, None, kw["delta"], kw["sum_out"], None, 1e-5, kw["gate"], 32)
+        d2, s2, g2 = held
+        assert args[0] == (None if d2 is None else d2.data_ptr()) and args[2] == (None if s2 is None else s2.data_ptr())
+        assert args[7] == (None if g2 is None else g2.data_ptr())
+        for t, src in ((d2, kw["delta"]), (g2, kw["gate"])):
+            if src is not None:
+                assert t.stride() == (64, 1) and t.data_ptr() != src.data_ptr() and torch.equal(t, src.reshape(3, 64))
+        assert s2 is None or s2.data_ptr() == kw["sum_out"].data_ptr()
 
 
 def test_takes_predicate():

@@ -8,19 +8,14 @@
 // flight per wave) against f(x) held in LDS as bf16.  A work-group owns whole rows of W (b, b + grid, ...) and its four
 // waves split K — with N = 4 480 rows (out_proj, down_proj) a wave per row leaves the 2 048 waves of the chip 2 or 3
 // rows each (73 % balance), a work-group per row 8 or 9 (97 %); the four partial sums meet in LDS.  f — the single-row
-// operator in front of the product — is computed in the prologue, redundantly in every work-group (x is a few KiB in L2):
-//   PRO_NONE      f(x) = x
-//   PRO_RMSNORM   s = bf16(x + delta) (written to `sum_out` by work-group 0: the new residual stream),
-//                 f = bf16(w * (s * rsqrt(mean(s^2) + eps)))             NemotronHRMSNorm + block add, modeling_nano.py:897-903, :966
-//   PRO_RELU2     f = bf16(relu(x)^2)                                    NemotronHMLP, :993-994
-//   PRO_GATED     v = x * silu(z), f = bf16(w * (v * rsqrt(mean_group(v^2) + eps)))     MambaRMSNormGated, :371-380
-// with the rounding points of the stand-alone kernels (norms.hip), so the fused step and the unfused one agree to the
-// accumulation order of the dot products.  fp32 accumulation (v_dot2c_f32_bf16), one rounding of y.
-#include "ssd_common.hpp"
+// operator in front of the product (PRO_*: linear_prologue.hpp, the contract shared with linear_rows.hip) — is computed in the
+// prologue, redundantly in every work-group (x is a few KiB in L2), with the rounding points of the stand-alone kernels
+// (norms.hip), so the fused step and the unfused one agree to the accumulation order of the dot products.  fp32
+// accumulation (v_dot2c_f32_bf16), one rounding of y.
+#include "linear_prologue.hpp"
 
 namespace {
 
-enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_RELU2 = 2, PRO_GATED = 3 };
 constexpr int GV_THREADS = 256;
 constexpr int GV_WAVES = GV_THREADS / 64;
 constexpr int GV_MAXM = 4;
@@ -39,28 +34,6 @@ struct GemvArgs {
   const bf16_t *conv_w, *conv_b;   // (channels, 4), (channels) or NULL
   int conv_lo, conv_hi;
 };
-
-// the 8 norm weights of one 16-byte piece of x: requested here (fp32 weights: two 16-byte loads, bf16: one), turned into
-// floats by normw_get — AFTER every other request of the prologue is out: a conversion next to the load is a wait for it
-struct NormW { f32x4 lo, hi; };
-__device__ __forceinline__ NormW normw_load(const void* w, int f32, int i0) {
-  // no branch: a value that arrives through one of two paths is copied where they join, and a copy is a wait for the load
-  const char* base = (const char*)w + (size_t)i0 * (f32 ? 4 : 2);
-  NormW r;
-  r.lo = *(const f32x4*)base;
-  r.hi = *(const f32x4*)(base + (f32 ? 16 : 0));       // (bf16 weights: the same 16 bytes again)
-  return r;
-}
-__device__ __forceinline__ void normw_get(const NormW& r, int f32, float (&out)[8]) {
-  if (f32) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { out[j] = r.lo[j]; out[4 + j] = r.hi[j]; }
-  } else {
-    const bf16x8 v = __builtin_bit_cast(bf16x8, r.lo);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[j] = (float)v[j];
-  }
-}
 
 // sum over the 64 lanes, as a wave-uniform value (DPP row shifts / broadcasts + one readlane: no LDS crossbar)
 __device__ __forceinline__ float wave_total(float v) {
@@ -97,7 +70,7 @@ __device__ __forceinline__ void gemv_prologue(const GemvArgs& a, bf16_t* fx, flo
         *(bf16x8*)(fr + 8 * iv) = v;
       }
     } else if (PRO == PRO_RMSNORM) {
-      constexpr int MAXV = 4;                        // K <= 8 * 256 * 4 (launcher)
+      constexpr int MAXV = 4;                        // K <= 8 * 256 * 4 (PRO_RMSNORM_MAX_K)
       float vals[MAXV][8];
       NormW wq[MAXV];                                // (the weights are requested with x, not behind the reduction)
       float ssq = 0.f;
@@ -214,12 +187,6 @@ __device__ __forceinline__ void gemv_prologue(const GemvArgs& a, bf16_t* fx, flo
   }
   __syncthreads();
 
-}
-
-// 16 bytes of W; NT: non-temporal (a weight byte is used once a token: it should not displace x / the norm weights in L2)
-template <bool NT>
-__device__ __forceinline__ bf16x8 ldw8(const bf16_t* p) {
-  return NT ? __builtin_nontemporal_load((const bf16x8*)p) : *(const bf16x8*)p;
 }
 
 // MT: 1 = one row of x (the batch-1 decode step), GV_MAXM = up to four (a.M);  R rows of W at a time, NB load
@@ -648,33 +615,11 @@ extern "C" int tv_gemv_bf16_fwd(const void* x, const void* W, const void* bias, 
                                 int norm_weight_dtype, float eps, const void* gate, int64_t gate_stride,
                                 int group_size, void* conv_state, const void* conv_weight, const void* conv_bias,
                                 int conv_row0, int conv_channels, void* stream) {
-  TV_CHECK_ARG(x && W && y, "gemv: null pointer");
-  TV_CHECK_ARG(M >= 1 && M <= GV_MAXM && N >= 1 && K >= 8, "gemv: M %d must be 1..%d, N %d >= 1, K %d >= 8", M, GV_MAXM, N, K);
-  if (K % 8 || ldw % 8 || x_stride % 8 || ((uintptr_t)x & 15) || ((uintptr_t)W & 15))
-    TV_UNSUPPORTED("gemv: K, the row strides of x and W must be multiples of 8 elements, x and W 16-byte aligned");
-  if ((size_t)M * K * 2 > 128 * 1024) TV_UNSUPPORTED("gemv: M x K = %d x %d does not fit the 128 KiB of LDS f(x) is held in", M, K);
-  TV_CHECK_ARG(prologue >= PRO_NONE && prologue <= PRO_GATED, "gemv: prologue %d", prologue);
   GemvArgs a;
-  a.x = (const bf16_t*)x; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.y = (bf16_t*)y;
-  a.delta = nullptr; a.gate = nullptr; a.norm_w = nullptr; a.sum_out = nullptr;
-  a.M = M; a.N = N; a.K = K; a.group = K; a.norm_w_f32 = 0;
-  a.xs = x_stride; a.ldw = ldw; a.ys = y_stride; a.ds = a.ss = a.gs = 0; a.eps = eps;
-  if (prologue == PRO_RMSNORM || prologue == PRO_GATED) {
-    TV_CHECK_ARG(norm_weight && (norm_weight_dtype == TV_F32 || norm_weight_dtype == TV_BF16), "gemv: norm weight (fp32 or bf16) needed");
-    a.norm_w = norm_weight; a.norm_w_f32 = norm_weight_dtype == TV_F32;
-  }
-  if (prologue == PRO_RMSNORM) {
-    if (K > 8 * GV_THREADS * 4) TV_UNSUPPORTED("gemv: rmsnorm prologue holds a row of <= %d channels", 8 * GV_THREADS * 4);
-    if (delta && (delta_stride % 8 || ((uintptr_t)delta & 15))) TV_UNSUPPORTED("gemv: delta must be 16-byte aligned rows");
-    if (sum_out && (sum_stride % 8 || ((uintptr_t)sum_out & 15))) TV_UNSUPPORTED("gemv: sum_out must be 16-byte aligned rows");
-    a.delta = (const bf16_t*)delta; a.ds = delta_stride; a.sum_out = (bf16_t*)sum_out; a.ss = sum_stride;
-  }
-  if (prologue == PRO_GATED) {
-    TV_CHECK_ARG(group_size > 0 && K % group_size == 0 && group_size % 8 == 0, "gemv: group size %d must divide K %d (multiple of 8)", group_size, K);
-    if (group_size > 8 * 64 * 4) TV_UNSUPPORTED("gemv: gated-norm prologue holds groups of <= %d channels", 8 * 64 * 4);
-    if (gate && (gate_stride % 8 || ((uintptr_t)gate & 15))) TV_UNSUPPORTED("gemv: gate must be 16-byte aligned rows");
-    a.gate = (const bf16_t*)gate; a.gs = gate_stride; a.group = group_size;
-  }
+  const int bad = linear_args_fill(a, "gemv", GV_MAXM, x, W, bias, y, M, N, K, x_stride, ldw, y_stride, prologue, delta, delta_stride,
+                                   sum_out, sum_stride, norm_weight, norm_weight_dtype, eps, gate, gate_stride, group_size);
+  if (bad != TV_OK) return bad;
+  if ((size_t)M * K * 2 > 128 * 1024) TV_UNSUPPORTED("gemv: M x K = %d x %d does not fit the 128 KiB of LDS f(x) is held in", M, K);
   a.conv_state = nullptr; a.conv_w = a.conv_b = nullptr; a.conv_lo = a.conv_hi = 0;
   if (conv_state) {
     TV_CHECK_ARG(conv_weight && conv_row0 >= 0 && conv_channels > 0 && conv_row0 + conv_channels <= N,

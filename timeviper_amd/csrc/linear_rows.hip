@@ -13,17 +13,16 @@
 // A work-group owns the tiles b, b + G, ... (at most 16: 4 accumulator registers each) and walks K in slices whose f(x)
 // fits its 72 KiB of LDS (two work-groups a CU), keeping the accumulators across the slices.  Inside a slice its four
 // waves split the steps into contiguous quarters; the four partial tiles meet in LDS once, after the last slice, and
-// are added in wave order: deterministic, no atomics.  f is gemv.hip's prologue set, with the rounding points and the
+// are added in wave order: deterministic, no atomics.  f is the prologue set of linear_prologue.hpp, with the rounding points and the
 // order of the sums of squares of the stand-alone kernels in norms.hip (so the same rstd, bit for bit):
 //   PRO_NONE / PRO_RELU2   elementwise, slice by slice
 //   PRO_RMSNORM            one pass over x (+ delta) for the M sums of squares — work-group 0 writes all M rows of the new
 //                          residual stream to `sum_out` there — then elementwise with the row's rstd; x lives in L2
 //   PRO_GATED              slices are whole norm groups: a wave per (row, group), statistics inside the slice
-#include "ssd_common.hpp"
+#include "linear_prologue.hpp"
 
 namespace {
 
-enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_RELU2 = 2, PRO_GATED = 3 };
 constexpr int LR_THREADS = 256;
 constexpr int LR_WAVES = LR_THREADS / 64;
 constexpr int LR_MAXM = 16;
@@ -42,28 +41,6 @@ struct RowsArgs {
   int64_t xs, ldw, ys, ds, ss, gs;
   float eps;
 };
-
-// (gemv.hip's normw_load / normw_get: the 8 norm weights of a 16-byte piece of x, requested without a branch, converted later)
-struct NormW { f32x4 lo, hi; };
-__device__ __forceinline__ NormW normw_load(const void* w, int f32, int i0) {
-  const char* base = (const char*)w + (size_t)i0 * (f32 ? 4 : 2);
-  NormW r;
-  r.lo = *(const f32x4*)base;
-  r.hi = *(const f32x4*)(base + (f32 ? 16 : 0));
-  return r;
-}
-__device__ __forceinline__ void normw_get(const NormW& r, int f32, float (&out)[8]) {
-  if (f32) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { out[j] = r.lo[j]; out[4 + j] = r.hi[j]; }
-  } else {
-    const bf16x8 v = __builtin_bit_cast(bf16x8, r.lo);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[j] = (float)v[j];
-  }
-}
-
-__device__ __forceinline__ bf16x8 ldw8(const bf16_t* p) { return __builtin_nontemporal_load((const bf16x8*)p); }
 
 // PRO_RMSNORM, once a work-group: stat[m] = rsqrt(mean(bf16(x + delta)[m]^2) + eps); work-group 0 writes the sums.
 // A thread's pieces and the order of the additions are rmsnorm_kernel's (norms.hip).
@@ -262,7 +239,7 @@ __global__ __launch_bounds__(LR_THREADS, 2) void linear_rows_kernel(RowsArgs a) 
 #pragma unroll
       for (int t = 0; t < TB; ++t)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) dst[t][i][q] = ldw8(wp[t] + o[q]);
+        for (int q = 0; q < 4; ++q) dst[t][i][q] = ldw8<true>(wp[t] + o[q]);
     }
   };
   auto mma = [&](const bf16x8 (&w)[TB][SB][4], f32x4 (&c)[TB], int s, int se, bool full) __attribute__((always_inline)) {
@@ -411,39 +388,12 @@ extern "C" int tv_linear_rows_bf16_fwd(const void* x, const void* W, const void*
                                        int64_t delta_stride, void* sum_out, int64_t sum_stride, const void* norm_weight,
                                        int norm_weight_dtype, float eps, const void* gate, int64_t gate_stride,
                                        int group_size, void* stream) {
-  TV_CHECK_ARG(x && W && y, "linear_rows: null pointer");
-  TV_CHECK_ARG(M >= 1 && M <= LR_MAXM && N >= 1 && K >= 8, "linear_rows: M %d must be 1..%d, N %d >= 1, K %d >= 8", M, LR_MAXM, N, K);
-  if (K % 8 || ldw % 8 || x_stride % 8 || ((uintptr_t)x & 15) || ((uintptr_t)W & 15))
-    TV_UNSUPPORTED("linear_rows: K, the row strides of x and W must be multiples of 8 elements, x and W 16-byte aligned");
-  TV_CHECK_ARG(prologue >= PRO_NONE && prologue <= PRO_GATED, "linear_rows: prologue %d", prologue);
-  TV_CHECK_ARG(ldw >= K && (M == 1 || (x_stride >= K && y_stride >= N)),
-               "linear_rows: row strides (x %lld, W %lld, y %lld) shorter than the rows (K %d, N %d)", (long long)x_stride,
-               (long long)ldw, (long long)y_stride, K, N);
   RowsArgs a;
-  a.x = (const bf16_t*)x; a.W = (const bf16_t*)W; a.bias = (const bf16_t*)bias; a.y = (bf16_t*)y;
-  a.delta = nullptr; a.gate = nullptr; a.norm_w = nullptr; a.sum_out = nullptr;
-  a.M = M; a.N = N; a.K = K; a.group = K; a.norm_w_f32 = 0; a.KS = 0; a.lds_stride = 0;
-  a.xs = x_stride; a.ldw = ldw; a.ys = y_stride; a.ds = a.ss = a.gs = 0; a.eps = eps;
-  if (prologue == PRO_RMSNORM || prologue == PRO_GATED) {
-    TV_CHECK_ARG(norm_weight && (norm_weight_dtype == TV_F32 || norm_weight_dtype == TV_BF16), "linear_rows: norm weight (fp32 or bf16) needed");
-    a.norm_w = norm_weight; a.norm_w_f32 = norm_weight_dtype == TV_F32;
-  }
-  if (prologue == PRO_RMSNORM) {
-    if (K > 8192) TV_UNSUPPORTED("linear_rows: rmsnorm prologue takes rows of <= %d channels", 8192);
-    if (delta && (delta_stride % 8 || ((uintptr_t)delta & 15))) TV_UNSUPPORTED("linear_rows: delta must be 16-byte aligned rows");
-    if (sum_out && (sum_stride % 8 || ((uintptr_t)sum_out & 15))) TV_UNSUPPORTED("linear_rows: sum_out must be 16-byte aligned rows");
-    TV_CHECK_ARG(M == 1 || ((!delta || delta_stride >= K) && (!sum_out || sum_stride >= K)),
-                 "linear_rows: delta / sum_out row strides shorter than K %d", K);
-    TV_CHECK_ARG(!sum_out || (sum_out != x && sum_out != delta), "linear_rows: sum_out must not alias x or delta");
-    a.delta = (const bf16_t*)delta; a.ds = delta_stride; a.sum_out = (bf16_t*)sum_out; a.ss = sum_stride;
-  }
-  if (prologue == PRO_GATED) {
-    TV_CHECK_ARG(group_size > 0 && K % group_size == 0 && group_size % 8 == 0, "linear_rows: group size %d must divide K %d (multiple of 8)", group_size, K);
-    if (group_size > 8 * 64 * 4) TV_UNSUPPORTED("linear_rows: gated-norm prologue holds groups of <= %d channels", 8 * 64 * 4);
-    if (gate && (gate_stride % 8 || ((uintptr_t)gate & 15))) TV_UNSUPPORTED("linear_rows: gate must be 16-byte aligned rows");
-    TV_CHECK_ARG(M == 1 || !gate || gate_stride >= K, "linear_rows: gate row stride shorter than K %d", K);
-    a.gate = (const bf16_t*)gate; a.gs = gate_stride; a.group = group_size;
-  }
+  const int bad = linear_args_fill(a, "linear_rows", LR_MAXM, x, W, bias, y, M, N, K, x_stride, ldw, y_stride, prologue, delta,
+                                   delta_stride, sum_out, sum_stride, norm_weight, norm_weight_dtype, eps, gate, gate_stride,
+                                   group_size);
+  if (bad != TV_OK) return bad;
+  a.KS = a.lds_stride = 0;                           // (launch_rows)
   hipStream_t st = (hipStream_t)stream;
   switch (prologue) {
     case PRO_NONE: return launch_rows<PRO_NONE>(a, st);

@@ -138,10 +138,11 @@ def bench_gemm(llm, st):
         nbytes = sum(m.weight.numel() * 2 for m in mods)
         for T in (1,) + tuple(d + 1 for d in DRAFTS):
             xs = [torch.randn(1, T, m.in_features, device=DEV).bfloat16() * 0.1 for m in mods]
+            route = nano.linear_route(xs[0])     # T = 1: tv_gemv_bf16_fwd where it applies, else the library GEMM
 
             def run():
                 for m, x in zip(mods, xs):
-                    nano._linear(m, x)           # T = 1: tv_gemv_bf16_fwd where it applies, else the library GEMM
+                    nano._linear(m, x, route)
             with torch.cuda.stream(st):
                 run()
                 st.synchronize()

@@ -712,6 +712,39 @@ def gemv_takes(x: torch.Tensor, weight: torch.Tensor) -> bool:
             and weight.stride(0) % 8 == 0)
 
 
+def _linear_operands(name, x, weight, bias, delta, sum_out, norm_weight, eps, gate, group_size):
+    """The operand checks gemv_fused and linear_rows_fused share (`name`: the wrapper, for the messages).  Returns the
+    (rows, K) view of x, in C order the arguments of tv_gemv_bf16_fwd / tv_linear_rows_bf16_fwd from `delta` to
+    `group_size`, and the tensors those pointers belong to — `_rows2d` may have copied delta / gate, and the caller must
+    hold the copies until the launch is queued."""
+    _gpu(x, weight, bias, delta, sum_out, norm_weight, gate)
+    K = x.shape[-1]
+    x2 = _rows2d(x)
+    if weight.dim() != 2 or weight.shape[1] != K:
+        raise TimeViperHipError(f"{name}: weight {tuple(weight.shape)} against rows of {K}")
+    # the C ABI carries no weight dtype: anything but dense bf16 rows would be re-interpreted silently
+    if (x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.stride(1) != 1 or weight.stride(0) % 8
+            or K % 8):
+        raise TimeViperHipError(f"{name}: bf16 x and weight with dense rows of a multiple of 8 elements only "
+                                f"(x {x.dtype}, weight {weight.dtype}, strides {tuple(weight.stride())}, K {K})")
+    d2 = None if delta is None else _rows2d(delta)
+    g2 = None if gate is None else _rows2d(gate)
+    s2 = None if sum_out is None else (sum_out if sum_out.dim() == 2 else sum_out.view(-1, K))   # (a view, or an error: never a copy)
+    for t in (d2, g2, s2):
+        if t is not None and (t.shape != x2.shape or t.dtype != x.dtype or t.stride(1) != 1):
+            raise TimeViperHipError(f"{name}: delta / gate / sum_out must have x's shape and dtype")
+    if bias is not None and (bias.dtype != x.dtype or not bias.is_contiguous() or bias.numel() != weight.shape[0]):
+        raise TimeViperHipError(f"{name}: bias must be N contiguous entries of x's dtype")
+    nw_dt = 0
+    if norm_weight is not None:
+        if not norm_weight.is_contiguous() or norm_weight.numel() != K:
+            raise TimeViperHipError(f"{name}: norm_weight must be a contiguous vector of K entries")
+        nw_dt = _dt(norm_weight)
+    stride = lambda t: 0 if t is None else t.stride(0)
+    return x2, (_p(d2), stride(d2), _p(s2), stride(s2), _p(norm_weight), nw_dt, float(eps), _p(g2), stride(g2),
+                int(group_size)), (d2, s2, g2)
+
+
 def gemv_fused(x, weight, bias=None, prologue=GEMV_NONE, delta=None, sum_out=None, norm_weight=None, eps=0.0,
                gate=None, group_size=0, conv=None):
     """y = f(x) @ weight.T (+ bias) for 1..4 rows — the linear layers of a decode step (torch.nn.Linear at q_len 1) with
@@ -720,31 +753,9 @@ def gemv_fused(x, weight, bias=None, prologue=GEMV_NONE, delta=None, sum_out=Non
     GEMV_GATED (MambaRMSNormGated with `gate`), rounding where the stand-alone operators round.
     `conv=(conv_state, weight, bias, row0)`: the outputs [row0, row0 + C) go through `causal_conv1d_update` (width 4,
     SiLU) on conv_state (B, C, 4) before they are stored — the mixer's in_proj -> conv pair as one launch (K < 8192)."""
-    _gpu(x, weight, bias, delta, sum_out, norm_weight, gate)
-    K = x.shape[-1]
-    x2 = _rows2d(x)
-    M, N = x2.shape[0], weight.shape[0]
-    if weight.shape[1] != K:
-        raise TimeViperHipError(f"gemv_fused: weight {tuple(weight.shape)} against rows of {K}")
-    # the C ABI carries no weight dtype: anything but dense bf16 rows would be re-interpreted silently
-    if (x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.stride(1) != 1 or weight.stride(0) % 8
-            or K % 8):
-        raise TimeViperHipError("gemv_fused: bf16 x and weight with dense rows of a multiple of 8 elements only "
-                                f"(x {x.dtype}, weight {weight.dtype}, strides {tuple(weight.stride())}, K {K})")
+    x2, pro_args, held = _linear_operands("gemv_fused", x, weight, bias, delta, sum_out, norm_weight, eps, gate, group_size)
+    (M, K), N = x2.shape, weight.shape[0]
     y = torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
-    d2 = None if delta is None else _rows2d(delta)
-    g2 = None if gate is None else _rows2d(gate)
-    s2 = None if sum_out is None else sum_out.view(-1, K)
-    for t in (d2, g2, s2):
-        if t is not None and (t.shape != x2.shape or t.dtype != x.dtype):
-            raise TimeViperHipError("gemv_fused: delta / gate / sum_out must have x's shape and dtype")
-    if bias is not None and (bias.dtype != x.dtype or not bias.is_contiguous()):
-        raise TimeViperHipError("gemv_fused: bias must be contiguous, of x's dtype")
-    nw_dt = 0
-    if norm_weight is not None:
-        if not norm_weight.is_contiguous() or norm_weight.numel() != K:
-            raise TimeViperHipError("gemv_fused: norm_weight must be a contiguous vector of K entries")
-        nw_dt = _dt(norm_weight)
     cst = cw = cb = None
     row0 = nch = 0
     if conv is not None:
@@ -756,9 +767,8 @@ def gemv_fused(x, weight, bias=None, prologue=GEMV_NONE, delta=None, sum_out=Non
             raise TimeViperHipError("gemv_fused: conv needs a contiguous (rows, C, 4) state and (C, 4) weight of x's dtype")
     check(_capi.lib().tv_gemv_bf16_fwd(
         _p(x2), _p(weight), _p(bias), _p(y), M, N, K, x2.stride(0), weight.stride(0), N, int(prologue),
-        _p(d2), 0 if d2 is None else d2.stride(0), _p(s2), 0 if s2 is None else s2.stride(0),
-        _p(norm_weight), nw_dt, float(eps), _p(g2), 0 if g2 is None else g2.stride(0), int(group_size),
-        _p(cst), _p(cw), _p(cb), int(row0), int(nch), _stream()), "tv_gemv_bf16_fwd")
+        *pro_args, _p(cst), _p(cw), _p(cb), int(row0), int(nch), _stream()), "tv_gemv_bf16_fwd")
+    del held                # (alive up to here: see _linear_operands)
     return y
 
 
@@ -790,42 +800,22 @@ def linear_rows_fused(x, weight, bias=None, prologue=GEMV_NONE, delta=None, sum_
     2 <= q_len <= 16 on one sequence), the weights streamed once, with gemv_fused's prologues (GEMV_*) and their rounding
     points; GEMV_RMSNORM writes every row of the sum to `sum_out`.  `out`: a bf16 (..., N) tensor to write, whose rows may
     be further apart than N (a column window of a wider buffer)."""
-    _gpu(x, weight, bias, delta, sum_out, norm_weight, gate, out)
-    K = x.shape[-1]
-    x2 = _rows2d(x)
-    M, N = x2.shape[0], weight.shape[0]
-    if weight.dim() != 2 or weight.shape[1] != K:
-        raise TimeViperHipError(f"linear_rows_fused: weight {tuple(weight.shape)} against rows of {K}")
-    if (x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.stride(1) != 1 or weight.stride(0) % 8
-            or K % 8):
-        raise TimeViperHipError("linear_rows_fused: bf16 x and weight with dense rows of a multiple of 8 elements only "
-                                f"(x {x.dtype}, weight {weight.dtype}, strides {tuple(weight.stride())}, K {K})")
+    x2, pro_args, held = _linear_operands("linear_rows_fused", x, weight, bias, delta, sum_out, norm_weight, eps, gate,
+                                    group_size)
+    (M, K), N = x2.shape, weight.shape[0]
     if out is None:
         y = torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
         y2 = y.view(-1, N)
     else:
+        _gpu(out)
         y = out
         if y.dtype != x.dtype or y.shape[-1] != N or y.numel() != M * N or y.stride(-1) != 1:
             raise TimeViperHipError(f"linear_rows_fused: out {tuple(y.shape)} {y.dtype} is not {M} bf16 rows of {N}")
         y2 = y if y.dim() == 2 else y.view(-1, N)     # (a view, or an error: never a copy)
-    d2 = None if delta is None else _rows2d(delta)
-    g2 = None if gate is None else _rows2d(gate)
-    s2 = None if sum_out is None else (sum_out if sum_out.dim() == 2 else sum_out.view(-1, K))
-    for t in (d2, g2, s2):
-        if t is not None and (t.shape != x2.shape or t.dtype != x.dtype or t.stride(1) != 1):
-            raise TimeViperHipError("linear_rows_fused: delta / gate / sum_out must have x's shape and dtype")
-    if bias is not None and (bias.dtype != x.dtype or not bias.is_contiguous() or bias.numel() != N):
-        raise TimeViperHipError("linear_rows_fused: bias must be N contiguous entries of x's dtype")
-    nw_dt = 0
-    if norm_weight is not None:
-        if not norm_weight.is_contiguous() or norm_weight.numel() != K:
-            raise TimeViperHipError("linear_rows_fused: norm_weight must be a contiguous vector of K entries")
-        nw_dt = _dt(norm_weight)
     check(_capi.lib().tv_linear_rows_bf16_fwd(
         _p(x2), _p(weight), _p(bias), _p(y2), M, N, K, x2.stride(0), weight.stride(0), y2.stride(0), int(prologue),
-        _p(d2), 0 if d2 is None else d2.stride(0), _p(s2), 0 if s2 is None else s2.stride(0),
-        _p(norm_weight), nw_dt, float(eps), _p(g2), 0 if g2 is None else g2.stride(0), int(group_size),
-        _stream()), "tv_linear_rows_bf16_fwd")
+        *pro_args, _stream()), "tv_linear_rows_bf16_fwd")
+    del held                # (alive up to here: see _linear_operands)
     return y
 
 

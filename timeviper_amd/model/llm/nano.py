@@ -480,24 +480,65 @@ class HybridMambaAttentionDynamicCache:
         return new_ssm_state
 
 
-# ------------------------------------------------------------------ decode-step helpers
-def _fused_decode(x: torch.Tensor) -> bool:
-    """The linear layers of a decode step (1..4 rows) run on tv_gemv_bf16_fwd with the operator in front of them in
-    the prologue; TV_DECODE_FUSED=0 keeps torch.nn.Linear + the stand-alone kernels (same arithmetic, library GEMV)."""
-    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3 and x.shape[1] == 1 and x.shape[0] <= 4
-            and not torch.is_grad_enabled() and os.environ.get("TV_DECODE_FUSED", "1") != "0")
-
-
+# ------------------------------------------------------------------ fused-step helpers
 ROWS_FUSED_DEFAULT = "0"       # what TV_ROWS_FUSED is taken to be when it is not set
 
 
-def _fused_rows(x: torch.Tensor) -> bool:
-    """The linear layers of a few-token forward on one sequence (2..16 rows: a continuation, a speculative step) run on
-    tv_linear_rows_bf16_fwd with the operator in front of them in the prologue under TV_ROWS_FUSED=1; without it (the
-    default until the step is measured faster on an MI355X) torch.nn.Linear + the stand-alone kernels
-    run (same arithmetic, library GEMM).  Read per call."""
-    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3 and x.shape[0] == 1 and 2 <= x.shape[1] <= 16
-            and not torch.is_grad_enabled() and os.environ.get("TV_ROWS_FUSED", ROWS_FUSED_DEFAULT) != "0")
+def is_continuation(past_key_values, cache_position) -> bool:
+    """A forward behind a finished prefill: a cache and a first position > 0 (one token: the decode step)."""
+    return past_key_values is not None and cache_position is not None and int(cache_position[0]) > 0
+
+
+def linear_route(x, cache=None, cache_position=None) -> Optional[str]:
+    """The kernel ONE linear layer runs on for x (B, T, K), by the tensor's device, dtype and shape and the switches (read
+    per call):
+      "gemv"  tv_gemv_bf16_fwd — one token of 1..4 sequences, unless TV_DECODE_FUSED=0;
+      "rows"  tv_linear_rows_bf16_fwd — 2..16 tokens of one sequence behind a prefill (a continuation, a speculative
+              step) under TV_ROWS_FUSED=1 (off by default until the step is measured faster on an MI355X, DESIGN.md
+              section 3);
+      None    torch.nn.Linear (library GEMM, same arithmetic)."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3 and not torch.is_grad_enabled()):
+        return None
+    B, T = x.shape[:2]
+    if T == 1 and B <= 4:
+        return "gemv" if os.environ.get("TV_DECODE_FUSED", "1") != "0" else None
+    if (B == 1 and 2 <= T <= 16 and os.environ.get("TV_ROWS_FUSED", ROWS_FUSED_DEFAULT) != "0"
+            and is_continuation(cache, cache_position)):
+        return "rows"
+    return None
+
+
+def fused_route(model, hidden, cache, cache_position, output_hidden_states=False) -> Optional[str]:
+    """The kernel a whole forward runs on, every block through its `step_fused` with the norms and activations in the
+    prologues of the products: `linear_route` of the residual stream, where nothing asks for per-layer outputs or NaN
+    checks, the hidden size is one the RMSNorm prologue holds and every matrix is bf16.  The decode step ("gemv") also needs
+    a prefill behind it and committed tokens (`_speculate` has no conv epilogue)."""
+    route = linear_route(hidden, cache, cache_position)
+    H = hidden.shape[-1]
+    if (route is None or output_hidden_states or model.check_nan or H % 8 or H > 8192
+            or not model._all_matrices_bf16()):
+        return None
+    if route == "gemv" and (not is_continuation(cache, cache_position) or getattr(cache, "speculating", False)):
+        return None
+    return route
+
+
+def _linear(mod: nn.Linear, x: torch.Tensor, route: Optional[str] = None) -> torch.Tensor:
+    """mod(x) on the kernel of `route` (`linear_route` of x) where that kernel takes the shapes."""
+    if route == "gemv" and K.gemv_takes(x, mod.weight):
+        return K.gemv_fused(x, mod.weight, mod.bias)
+    if route == "rows" and K.linear_rows_takes(x, mod.weight):
+        return K.linear_rows_fused(x, mod.weight, mod.bias)
+    return mod(x)
+
+
+def _norm_linear(lin, hidden, delta, norm, weight, bias, **kw):
+    """A block's first product with its RMSNorm (+ the pending residual add, written to a new residual stream) in the
+    prologue of `lin` (K.gemv_fused / K.linear_rows_fused).  Returns (residual stream, product)."""
+    new_hidden = torch.empty_like(hidden) if delta is not None else hidden
+    y = lin(hidden, weight, bias, K.GEMV_RMSNORM, delta=delta, sum_out=new_hidden if delta is not None else None,
+            norm_weight=norm.weight, eps=norm.variance_epsilon, **kw)
+    return new_hidden, y
 
 
 # a continuation (T > 1 tokens behind a prefill) of up to this many tokens updates the SSM state in place, token by token
@@ -511,19 +552,6 @@ CONTINUE_LAST_PATH = None      # "seq" / "scan": what the most recent Mamba cont
 
 def continue_t_seq() -> int:
     return int(os.environ.get("TV_CONTINUE_TSEQ", CONTINUE_T_SEQ))
-
-
-def is_continuation(past_key_values, cache_position) -> bool:
-    """A forward behind a finished prefill: a cache and a first position > 0 (one token: the decode step)."""
-    return past_key_values is not None and cache_position is not None and int(cache_position[0]) > 0
-
-
-def _linear(mod: nn.Linear, x: torch.Tensor, continuation: bool = False) -> torch.Tensor:
-    if _fused_decode(x) and K.gemv_takes(x, mod.weight):
-        return K.gemv_fused(x, mod.weight, mod.bias)
-    if continuation and _fused_rows(x) and K.linear_rows_takes(x, mod.weight):
-        return K.linear_rows_fused(x, mod.weight, mod.bias)
-    return mod(x)
 
 
 # ------------------------------------------------------------------ layers
@@ -609,28 +637,13 @@ class NemotronHMamba2Mixer(nn.Module):
         if attention_mask is not None and attention_mask.shape[1] > 1 and attention_mask.shape[0] > 1:
             hidden_states = (hidden_states * attention_mask[:, :, None]).to(hidden_states.dtype)
         projected_states = self.in_proj(hidden_states)
-        gts = self.n_groups * self.ssm_state_size
+        if is_continuation(cache_params, cache_position):
+            gate, y = self._recur(cache_params, projected_states)
+            return self.out_proj(self.norm(y, gate))
         d_in = self.intermediate_size
-        decode = (cache_params is not None and cache_position is not None
-                  and int(cache_position[0]) > 0)
         gate, xBC, dt = projected_states.split([d_in, self.conv_dim, self.num_heads], dim=-1)
         w = self.conv1d.weight.squeeze(1)
         negA, D32, dtb32 = self._consts()
-        if decode and getattr(cache_params, "speculating", False):
-            return self._speculate(cache_params, gate, projected_states, w, negA, D32, dtb32)
-        if decode and seq_len > 1:
-            return self._continue(cache_params, gate, xBC, dt, w, negA, D32, dtb32)
-        if decode:
-            xBC = K.causal_conv1d_update(xBC[:, 0], cache_params.conv_states[self.layer_idx], w,
-                                         self.conv1d.bias, self.activation)
-            x, Bm, Cm = torch.split(xBC, [d_in, gts, gts], dim=-1)
-            y = K.selective_state_update(
-                cache_params.ssm_states[self.layer_idx],
-                x.reshape(batch_size, self.num_heads, self.head_dim), dt[:, 0], negA,
-                Bm.reshape(batch_size, self.n_groups, -1), Cm.reshape(batch_size, self.n_groups, -1),
-                D32, z=None, dt_bias=dtb32, dt_softplus=True)
-            y = self.norm(y.reshape(batch_size, 1, d_in), gate)
-            return self.out_proj(y)
 
         if cache_params is not None:  # conv state = last K pre-conv inputs, (B, C, K)  (:596-610)
             Kw = self.conv_kernel_size
@@ -660,11 +673,11 @@ class NemotronHMamba2Mixer(nn.Module):
             return out, ssm_state, res[2]
         return out
 
-    def _continue(self, cache_params, gate, xBC, dt, w, negA, D32, dtb32, finish=True):
+    def _continue(self, cache_params, xBC, dt, w, negA, D32, dtb32):
         """T > 1 tokens behind a prefill (or earlier continuations / decode steps): the conv starts from the cached
         pre-conv rows, the recurrence from the cached state.  Up to `continue_t_seq()` tokens the state stays where it
         is (tv_selective_state_update_seq: every row read and written once); longer runs take the chunked scan with
-        the cached state as its initial state.  `finish=False` returns y in front of the gated norm (rows_fused)."""
+        the cached state as its initial state.  Returns y in front of the gated norm."""
         global CONTINUE_LAST_PATH
         batch_size, seq_len, _ = xBC.shape
         d_in, Kw, idx = self.intermediate_size, self.conv_kernel_size, self.layer_idx
@@ -688,17 +701,13 @@ class NemotronHMamba2Mixer(nn.Module):
             y = K.selective_state_update_seq(cache_params.ssm_states[idx], x, dt, negA, Bm, Cm, D=D32, dt_bias=dtb32,
                                              dt_softplus=True, dt_limit=self.time_step_limit, group_map=self.group_map)
         CONTINUE_LAST_PATH = "scan" if scan else "seq"
-        y = y.reshape(batch_size, seq_len, d_in)
-        if not finish:
-            return y
-        return self.out_proj(self.norm(y, gate))
+        return y.reshape(batch_size, seq_len, d_in)
 
-    def _speculate(self, cache_params, gate, projected_states, w, negA, D32, dtb32, finish=True):
+    def _speculate(self, cache_params, projected_states, w, negA, D32, dtb32):
         """T >= 1 provisional tokens (cache.begin_speculation): the cache's conv / SSM states advance by the tokens KEPT
         of the previous forward only — the conv state by a gather, the SSM state inside the commit phase of
         tv_selective_state_update_spec — and this forward's tokens are computed from there without being stored.  Their
-        operands stay in the cache's slot for the next forward's commit phase.  `finish=False` returns y in front of the
-        gated norm (rows_fused)."""
+        operands stay in the cache's slot for the next forward's commit phase.  Returns y in front of the gated norm."""
         batch_size, seq_len, _ = projected_states.shape
         d_in, idx = self.intermediate_size, self.layer_idx
         sp = cache_params._spec
@@ -715,59 +724,50 @@ class NemotronHMamba2Mixer(nn.Module):
         y = K.selective_state_update_spec(cache_params.ssm_states[idx], prev, sp["n_commit"], new, negA, D=D32,
                                           dt_bias=dtb32, dt_softplus=True, dt_limit=self.time_step_limit,
                                           group_map=self.group_map)
-        y = y.reshape(batch_size, seq_len, d_in)
-        if not finish:
-            return y
-        return self.out_proj(self.norm(y, gate))
+        return y.reshape(batch_size, seq_len, d_in)
 
-    def rows_fused(self, hidden, delta, norm, cache_params):
-        """A few tokens behind a prefill (`_fused_rows`), committed or provisional: the block's RMSNorm (+ residual add)
-        inside in_proj, `_continue` / `_speculate` up to the gated norm, the gated norm inside out_proj.  Returns
-        (residual stream, mixer output)."""
-        new_hidden = torch.empty_like(hidden) if delta is not None else hidden
-        d_in = self.intermediate_size
-        proj = K.linear_rows_fused(hidden, self.in_proj.weight, self.in_proj.bias, K.GEMV_RMSNORM, delta=delta,
-                                   sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
-                                   eps=norm.variance_epsilon)
-        gate, xBC, dt = proj.split([d_in, self.conv_dim, self.num_heads], dim=-1)
-        w = self.conv1d.weight.squeeze(1)
-        negA, D32, dtb32 = self._consts()
-        if getattr(cache_params, "speculating", False):
-            y = self._speculate(cache_params, gate, proj, w, negA, D32, dtb32, finish=False)
-        else:
-            y = self._continue(cache_params, gate, xBC, dt, w, negA, D32, dtb32, finish=False)
-        out = K.linear_rows_fused(y, self.out_proj.weight, self.out_proj.bias, K.GEMV_GATED,
-                                  norm_weight=self.norm.weight, eps=self.norm.variance_epsilon, gate=gate,
-                                  group_size=self.norm.group_size)
-        return new_hidden, out
-
-    def decode_fused(self, hidden, delta, norm, cache_params):
-        """One decode token with the block's RMSNorm (+ residual add) inside in_proj and the gated norm inside out_proj:
-        in_proj (+ conv update in its epilogue) -> state update -> out_proj, 3 launches.  Returns (residual stream, mixer output)."""
-        B = hidden.shape[0]
-        new_hidden = torch.empty_like(hidden) if delta is not None else hidden
-        gts = self.n_groups * self.ssm_state_size
-        d_in = self.intermediate_size
-        conv_state = cache_params.conv_states[self.layer_idx]
-        w = self.conv1d.weight.squeeze(1)
-        # the conv update rides in the product's epilogue where the kernel offers it (width 4, SiLU, K < 8192)
-        conv_in = (self.conv_kernel_size == 4 and self.activation in ("silu", "swish") and hidden.shape[-1] < 8192
-                   and conv_state.dtype == hidden.dtype and conv_state.is_contiguous() and w.is_contiguous())
-        proj = K.gemv_fused(hidden, self.in_proj.weight, self.in_proj.bias, K.GEMV_RMSNORM, delta=delta,
-                            sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
-                            eps=norm.variance_epsilon,
-                            conv=(conv_state, w, self.conv1d.bias, d_in) if conv_in else None)
-        gate, xBC, dt = proj.split([d_in, self.conv_dim, self.num_heads], dim=-1)
-        negA, D32, dtb32 = self._consts()
-        xBC = xBC[:, 0] if conv_in else K.causal_conv1d_update(xBC[:, 0], conv_state, w, self.conv1d.bias, self.activation)
+    def _decode(self, cache_params, xBC, dt, w, negA, D32, dtb32, conv_done=False):
+        """One token per sequence: the conv update (unless the product's epilogue did it: `conv_done`), the x | B | C
+        split, the state update.  Returns y in front of the gated norm."""
+        batch_size = xBC.shape[0]
+        d_in, gts, idx = self.intermediate_size, self.n_groups * self.ssm_state_size, self.layer_idx
+        xBC = xBC[:, 0] if conv_done else K.causal_conv1d_update(xBC[:, 0], cache_params.conv_states[idx], w,
+                                                                 self.conv1d.bias, self.activation)
         x, Bm, Cm = torch.split(xBC, [d_in, gts, gts], dim=-1)
         y = K.selective_state_update(
-            cache_params.ssm_states[self.layer_idx], x.reshape(B, self.num_heads, self.head_dim), dt[:, 0], negA,
-            Bm.reshape(B, self.n_groups, -1), Cm.reshape(B, self.n_groups, -1), D32, z=None, dt_bias=dtb32,
-            dt_softplus=True)
-        out = K.gemv_fused(y.reshape(B, 1, d_in), self.out_proj.weight, self.out_proj.bias, K.GEMV_GATED,
-                           norm_weight=self.norm.weight, eps=self.norm.variance_epsilon, gate=gate,
-                           group_size=self.norm.group_size)
+            cache_params.ssm_states[idx], x.reshape(batch_size, self.num_heads, self.head_dim), dt[:, 0], negA,
+            Bm.reshape(batch_size, self.n_groups, -1), Cm.reshape(batch_size, self.n_groups, -1), D32, z=None,
+            dt_bias=dtb32, dt_softplus=True)
+        return y.reshape(batch_size, 1, d_in)
+
+    def _recur(self, cache_params, projected_states, conv_done=False):
+        """The tokens of a forward behind a prefill, from in_proj's output to the gated norm's operands (gate, y):
+        provisional tokens, several committed ones, or one."""
+        gate, xBC, dt = projected_states.split([self.intermediate_size, self.conv_dim, self.num_heads], dim=-1)
+        w = self.conv1d.weight.squeeze(1)
+        consts = self._consts()
+        if getattr(cache_params, "speculating", False):
+            return gate, self._speculate(cache_params, projected_states, w, *consts)
+        if projected_states.shape[1] > 1:
+            return gate, self._continue(cache_params, xBC, dt, w, *consts)
+        return gate, self._decode(cache_params, xBC, dt, w, *consts, conv_done)
+
+    def step_fused(self, lin, hidden, delta, norm, cache_params):
+        """A forward behind a prefill with the block's RMSNorm (+ residual add) inside in_proj and the gated norm inside
+        out_proj: in_proj -> `_recur` -> out_proj (one token: 3 launches).  Returns (residual stream, mixer output)."""
+        conv = None
+        if hidden.shape[1] == 1:
+            # one token (the gemv route): the conv update rides in the product's epilogue where the kernel offers it
+            # (width 4, SiLU, K < 8192)
+            conv_state, w = cache_params.conv_states[self.layer_idx], self.conv1d.weight.squeeze(1)
+            if (self.conv_kernel_size == 4 and self.activation in ("silu", "swish") and hidden.shape[-1] < 8192
+                    and conv_state.dtype == hidden.dtype and conv_state.is_contiguous() and w.is_contiguous()):
+                conv = (conv_state, w, self.conv1d.bias, self.intermediate_size)
+        new_hidden, proj = _norm_linear(lin, hidden, delta, norm, self.in_proj.weight, self.in_proj.bias,
+                                        **({} if conv is None else {"conv": conv}))
+        gate, y = self._recur(cache_params, proj, conv_done=conv is not None)
+        out = lin(y, self.out_proj.weight, self.out_proj.bias, K.GEMV_GATED, norm_weight=self.norm.weight,
+                  eps=self.norm.variance_epsilon, gate=gate, group_size=self.norm.group_size)
         return new_hidden, out
 
 
@@ -790,21 +790,10 @@ class NemotronHMLP(nn.Module):
         # `act_fn` stays for the module tree; the activation runs as one in-place HIP pass
         return self.down_proj(K.relu2(self.up_proj(x), inplace=True))
 
-    def decode_fused(self, hidden, delta, norm):
-        """One decode token: RMSNorm (+ residual add) inside up_proj, relu^2 inside down_proj — 2 launches."""
-        new_hidden = torch.empty_like(hidden) if delta is not None else hidden
-        u = K.gemv_fused(hidden, self.up_proj.weight, self.up_proj.bias, K.GEMV_RMSNORM, delta=delta,
-                         sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
-                         eps=norm.variance_epsilon)
-        return new_hidden, K.gemv_fused(u, self.down_proj.weight, self.down_proj.bias, K.GEMV_RELU2)
-
-    def rows_fused(self, hidden, delta, norm):
-        """A few tokens (`_fused_rows`): RMSNorm (+ residual add) inside up_proj, relu^2 inside down_proj — 2 launches."""
-        new_hidden = torch.empty_like(hidden) if delta is not None else hidden
-        u = K.linear_rows_fused(hidden, self.up_proj.weight, self.up_proj.bias, K.GEMV_RMSNORM, delta=delta,
-                                sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
-                                eps=norm.variance_epsilon)
-        return new_hidden, K.linear_rows_fused(u, self.down_proj.weight, self.down_proj.bias, K.GEMV_RELU2)
+    def step_fused(self, lin, hidden, delta, norm, cache_params=None):
+        """RMSNorm (+ residual add) inside up_proj, relu^2 inside down_proj — 2 launches (the cache is not used)."""
+        new_hidden, u = _norm_linear(lin, hidden, delta, norm, self.up_proj.weight, self.up_proj.bias)
+        return new_hidden, lin(u, self.down_proj.weight, self.down_proj.bias, K.GEMV_RELU2)
 
 
 class NemotronHAttention(nn.Module):
@@ -834,27 +823,29 @@ class NemotronHAttention(nn.Module):
                                       "under flash_attention_2, reference :2208-2213)")
         bsz, q_len, _ = hidden_states.size()
         cont = is_continuation(past_key_value, cache_position)
-        q = _linear(self.q_proj, hidden_states, cont).view(bsz, q_len, self.num_heads, self.head_dim)
-        k = _linear(self.k_proj, hidden_states, cont).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
-        v = _linear(self.v_proj, hidden_states, cont).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
-        if getattr(past_key_value, "speculating", False) and cont:
-            o = self._attend_provisional(q, k, v, past_key_value)
-            o = _linear(self.o_proj, o.reshape(bsz, q_len, self.num_heads * self.head_dim), True)
-            return o, None, past_key_value
-        if past_key_value is not None:
-            k, v = past_key_value.update(k, v, self.layer_idx)
-        if past_key_value is not None and q_len == 1 and past_key_value.static_decode:
-            # static decode: the whole buffers + the key count on the device (same launch parameters every token)
-            kb, vb = past_key_value.kv_buffers(self.layer_idx)
-            o = K.flash_attn_decode(q, kb, vb, seqlens_k=past_key_value.decode_lens(self.layer_idx))
-        elif q_len > 1 and is_continuation(past_key_value, cache_position):
-            # a continuation: the T new rows are in the cache, the T queries are its last T tokens (split-KV kernel)
-            o = K.flash_attn_append(q, k, v)
-        else:
-            o = K._flash_attention_forward(q, k, v, attention_mask=None, query_length=q_len,
-                                           is_causal=self.is_causal)
-        o = _linear(self.o_proj, o.reshape(bsz, q_len, self.num_heads * self.head_dim), cont)
+        route = linear_route(hidden_states, past_key_value, cache_position)
+        q = _linear(self.q_proj, hidden_states, route).view(bsz, q_len, self.num_heads, self.head_dim)
+        k = _linear(self.k_proj, hidden_states, route).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
+        v = _linear(self.v_proj, hidden_states, route).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
+        o = self._attend(q, k, v, past_key_value, cont)
+        o = _linear(self.o_proj, o.reshape(bsz, q_len, self.num_heads * self.head_dim), route)
         return o, None, past_key_value
+
+    def _attend(self, q, k, v, cache, continuation):
+        """The new keys / values into the cache (if any) and the attention of the new queries over all of it."""
+        q_len = q.shape[1]
+        if continuation and getattr(cache, "speculating", False):
+            return self._attend_provisional(q, k, v, cache)
+        if cache is not None:
+            k, v = cache.update(k, v, self.layer_idx)
+        if cache is not None and q_len == 1 and cache.static_decode:
+            # static decode: the whole buffers + the key count on the device (same launch parameters every token)
+            kb, vb = cache.kv_buffers(self.layer_idx)
+            return K.flash_attn_decode(q, kb, vb, seqlens_k=cache.decode_lens(self.layer_idx))
+        if continuation and q_len > 1:
+            # a continuation: the T new rows are in the cache, the T queries are its last T tokens (split-KV kernel)
+            return K.flash_attn_append(q, k, v)
+        return K._flash_attention_forward(q, k, v, attention_mask=None, query_length=q_len, is_causal=self.is_causal)
 
     def _attend_provisional(self, q, k, v, cache):
         """The attention of a speculative step: the T rows go behind the committed ones (rejected rows are overwritten by
@@ -876,46 +867,19 @@ class NemotronHAttention(nn.Module):
             self._qkv_key = key
         return self._qkv_cat
 
-    def decode_fused(self, hidden, delta, norm, cache):
-        """One decode token: the block's RMSNorm (+ residual add) in the prologue of ONE q / k / v product, cache append,
-        split-KV attention, o_proj — 4 launches + the cache writes, against 7."""
-        B = hidden.shape[0]
-        new_hidden = torch.empty_like(hidden) if delta is not None else hidden
-        nq, nkv = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
-        qkv = K.gemv_fused(hidden, self._qkv_weight(), None, K.GEMV_RMSNORM, delta=delta,
-                           sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
-                           eps=norm.variance_epsilon)
-        q, k, v = qkv.split([nq, nkv, nkv], dim=-1)
-        q = q.view(B, 1, self.num_heads, self.head_dim)
-        k = k.view(B, 1, self.num_key_value_heads, self.head_dim)
-        v = v.view(B, 1, self.num_key_value_heads, self.head_dim)
-        kc, vc = cache.update(k, v, self.layer_idx)
-        if cache.static_decode:
-            kb, vb = cache.kv_buffers(self.layer_idx)
-            o = K.flash_attn_decode(q, kb, vb, seqlens_k=cache.decode_lens(self.layer_idx))
-        else:
-            o = K._flash_attention_forward(q, kc, vc, attention_mask=None, query_length=1, is_causal=self.is_causal)
-        return new_hidden, _linear(self.o_proj, o.reshape(B, 1, nq))
-
-    def rows_fused(self, hidden, delta, norm, cache):
-        """A few tokens behind a prefill (`_fused_rows`), committed or provisional: the block's RMSNorm (+ residual add) in
-        the prologue of ONE q / k / v product, the cache writes, split-KV attention, o_proj."""
+    def step_fused(self, lin, hidden, delta, norm, cache):
+        """A forward behind a prefill: the block's RMSNorm (+ residual add) in the prologue of ONE q / k / v product,
+        the cache writes, split-KV attention, o_proj — one token: 4 launches + the cache writes, against 7."""
         B, T = hidden.shape[:2]
-        new_hidden = torch.empty_like(hidden) if delta is not None else hidden
         nq, nkv = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
-        qkv = K.linear_rows_fused(hidden, self._qkv_weight(), None, K.GEMV_RMSNORM, delta=delta,
-                                  sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
-                                  eps=norm.variance_epsilon)
+        new_hidden, qkv = _norm_linear(lin, hidden, delta, norm, self._qkv_weight(), None)
         q, k, v = qkv.split([nq, nkv, nkv], dim=-1)
         q = q.view(B, T, self.num_heads, self.head_dim)
         k = k.view(B, T, self.num_key_value_heads, self.head_dim)
         v = v.view(B, T, self.num_key_value_heads, self.head_dim)
-        if getattr(cache, "speculating", False):
-            o = self._attend_provisional(q, k, v, cache)
-        else:
-            kc, vc = cache.update(k, v, self.layer_idx)
-            o = K.flash_attn_append(q, kc, vc)
-        return new_hidden, K.linear_rows_fused(o.reshape(B, T, nq), self.o_proj.weight, None, K.GEMV_NONE)
+        o = self._attend(q, k, v, cache, True).reshape(B, T, nq)
+        # (one token: `_linear`, which asks gemv_takes for the shape; several: the rows kernel takes every shape)
+        return new_hidden, (_linear(self.o_proj, o, "gemv") if T == 1 else lin(o, self.o_proj.weight, None, K.GEMV_NONE))
 
 
 NemotronHFlashAttention2 = NemotronHAttention
@@ -1122,15 +1086,12 @@ class NemotronHModel(PdropMixin, nn.Module):
                 raise RuntimeError(f"speculation: {hidden.shape[1]} tokens in one forward, more than continue_t_seq() = "
                                    f"{continue_t_seq()} (the range of the in-register recurrence)")
             past_key_values.spec_begin_forward(hidden.shape[1])
-        fused_step = (_fused_decode(hidden) and not speculating and past_key_values is not None and cache_position is not None
-                      and int(cache_position[0]) > 0 and not output_hidden_states and not self.check_nan
-                      and hidden.shape[-1] % 8 == 0 and hidden.shape[-1] <= 8192
-                      and self._all_matrices_bf16())
-        # the same route for the 2..16 tokens of a continuation or a speculative step (tv_linear_rows_bf16_fwd)
-        rows_step = (_fused_rows(hidden) and continuation and not output_hidden_states and not self.check_nan
-                     and hidden.shape[-1] % 8 == 0 and hidden.shape[-1] <= 8192 and self._all_matrices_bf16())
+        # a decode step / a few tokens behind a prefill: every block's norm (+ add) and activation run in the prologues of
+        # its products (`fused_route`); resolved per call, so that a replaced K.gemv_fused / K.linear_rows_fused is seen
+        route = fused_route(self, hidden, past_key_values, cache_position, output_hidden_states)
+        lin = getattr(K, {"gemv": "gemv_fused", "rows": "linear_rows_fused"}[route]) if route else None
         # attention blocks join when their projections carry no bias (the stacked q / k / v product takes none)
-        attn_fused = (fused_step or rows_step) and not self.config.attention_bias
+        attn_fused = not self.config.attention_bias
         for layer_idx, block in enumerate(self.layers):
             if self.use_pdrop and train_pdrop_args is not None \
                     and layer_idx in self.pdrop_layers \
@@ -1153,18 +1114,8 @@ class NemotronHModel(PdropMixin, nn.Module):
             if output_hidden_states:
                 all_hidden += ((hidden if delta is None else hidden + delta),)
             # x_{i+1} = x_i + mixer(norm(x_i)); the add of layer i-1 is fused into this norm
-            if fused_step and (block.block_type != "attention" or attn_fused):
-                # decode token: the norm (+ add) runs in the prologue of the block's first matrix-vector product
-                if block.block_type == "mlp":
-                    hidden, delta = block.mixer.decode_fused(hidden, delta, block.norm)
-                else:
-                    hidden, delta = block.mixer.decode_fused(hidden, delta, block.norm, past_key_values)
-                continue
-            if rows_step and (block.block_type != "attention" or attn_fused):
-                if block.block_type == "mlp":
-                    hidden, delta = block.mixer.rows_fused(hidden, delta, block.norm)
-                else:
-                    hidden, delta = block.mixer.rows_fused(hidden, delta, block.norm, past_key_values)
+            if route and (block.block_type != "attention" or attn_fused):
+                hidden, delta = block.mixer.step_fused(lin, hidden, delta, block.norm, past_key_values)
                 continue
             if delta is None:
                 normed = block.norm(hidden)
@@ -1253,7 +1204,7 @@ class NemotronHForCausalLM(nn.Module):
         keep = self.config.num_logits_to_keep if logits_to_keep is None else logits_to_keep
         if isinstance(keep, int) and keep > 0:
             hidden = hidden[:, -keep:]
-        logits = _linear(self.lm_head, hidden.to(self.lm_head.weight.dtype),
-                         is_continuation(past_key_values, cache_position)).float()
+        hidden = hidden.to(self.lm_head.weight.dtype)
+        logits = _linear(self.lm_head, hidden, linear_route(hidden, past_key_values, cache_position)).float()
         return CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=out.past_key_values,
                                       hidden_states=out.hidden_states)

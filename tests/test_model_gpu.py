@@ -180,6 +180,48 @@ def test_vit_vs_oracle():
     assert relerr(out, ref) < 2e-2
 
 
+VIT_FRAME_BOUND = 2e-2
+
+
+@pytest.fixture(scope="module")
+def vit_many_frames():
+    """The toy ViT of test_vit_vs_oracle (same seed, same weights), its 3 frames followed by 2 046 more, and the
+    oracle's output — once for both forms, released with the module."""
+    from timeviper_amd.model.vit.siglip import VisionTransformer
+    torch.manual_seed(0)
+    vit = VisionTransformer(img_size=56, patch_size=14, embed_dim=144, depth=4, num_heads=2, mlp_hidden=256)
+    for p in vit.parameters():
+        if p.dim() > 1:
+            torch.nn.init.normal_(p, std=0.05)
+    pix = torch.cat([torch.randn(3, 3, 56, 56), torch.randn(2046, 3, 56, 56)])
+    sd = {k: v.detach().bfloat16().float() for k, v in vit.state_dict().items()}
+    ref = ov.vit_intermediate_ref(sd, pix.bfloat16().float(), depth=4, num_heads=2, patch=14)
+    yield vit.to(DEV).bfloat16(), pix.to(DEV).bfloat16(), ref.double()
+
+
+@pytest.mark.parametrize("stream", ["1", "0"], ids=["stream", "fused"])
+def test_vit_vs_oracle_many_rows_per_frame(monkeypatch, vit_many_frames, stream):
+    """2 049 frames x 16 patches = 32 784 rows (4 098 waves of 8: the last block runs 2 of its 4 waves): in the stream
+    form (TV_VIT_STREAM unset / 1) every LayerNorm runs on the many-row kernel with a row bias from the second one on;
+    with TV_VIT_STREAM=0 the fused form's LayerNorms carry a residual and run on the wave kernel at the same row count.
+    Judged per FRAME (a wrong row among 32 784 does not move a global relative error).  The first three frames are
+    test_vit_vs_oracle's frames on the same weights.  Measured on an MI355X, worst per-frame relative error of those
+    three: 4.94e-3 (stream), 4.88e-3 (TV_VIT_STREAM=0); of all 2 049: 5.38e-3 and 5.05e-3.  The bound of that test, 2e-2, is
+    4.0 times the larger three-frame figure — more than the factor 2 asked of it — so it stands as the per-frame
+    bound, and the test asserts that margin on what it measures."""
+    monkeypatch.setenv("TV_VIT_STREAM", stream)
+    vit, pix, ref = vit_many_frames
+    with torch.no_grad():
+        out = vit(pix)
+    assert out.shape == (2049, 16, 144)
+    err = (out.double().cpu() - ref).flatten(1).norm(dim=1) / ref.flatten(1).norm(dim=1)
+    worst, three = int(err.argmax()), float(err[:3].max())
+    print(f"vit per-frame relerr (TV_VIT_STREAM={stream}): worst {float(err[worst]):.3e} at frame {worst}, "
+          f"first three frames {three:.3e}")
+    assert VIT_FRAME_BOUND >= 2 * three, f"2e-2 is not twice the three-frame worst {three:.3e}"
+    assert bool(torch.isfinite(err).all()) and float(err[worst]) < VIT_FRAME_BOUND, (worst, float(err[worst]))
+
+
 @pytest.mark.parametrize("case,is_video", [("video", True), ("video_b2", True), ("images", False)])
 def test_internvideo2_tower_vs_reference_golden(case, is_video):
     """InternVideo2 tower on the HIP operators (bf16) against the reference's own fp32

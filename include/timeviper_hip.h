@@ -478,6 +478,31 @@ int tv_attn_append_fwd(const void* q, const void* k, const void* v, void* o, voi
 /* launches of tv_attn_append_fwd by this process so far (tests: a call did not fall back) */
 int tv_attn_append_calls(void);
 
+/* The same split-KV walk for BRANCHES: ONE query token of each of `branches` = B sequences that share ONE prefix (a
+ * prefilled video asked several questions at once) and hold a suffix each.  q, o (B, Hq, D) by branch / head strides;
+ * k_prefix / v_prefix ONE sequence (prefix_len, Hkv, D) by row / head strides, prefix_len >= 1, seen whole by every branch;
+ * k_suffix / v_suffix (B, suffix_cap, Hkv, D) by branch / row / head strides: branch b sees its own rows [0, n_b) and
+ * nothing of another branch.  seqlens_suffix: NULL (n_b = suffix_cap for all), or DEVICE memory holding B ints, each
+ * clamped to [0, suffix_cap] — as tv_attn_decode_fwd's seqlens_k, so that a captured step replays against growing
+ * suffixes; n_b = 0 is the prefix alone.  lse (B, Hq) fp32 or NULL.  The 16 MFMA columns of a prefix work-group hold
+ * (branch c / gq, head c % gq) of a kv-head, in blocks of 16: the prefix is read once per kv-head and block, never per
+ * branch; the suffix of a branch is walked by work-groups of the same launch, and the merge launch reduces the prefix
+ * and suffix partials (rows at and beyond n_b are never read).  Supported: headdim 128, bf16, B <= 16 and
+ * B * (Hq / Hkv) <= 128 columns; anything else returns TV_ERR_UNSUPPORTED (callers: tv_attn_decode_fwd per branch on the
+ * concatenated keys).  No atomics, no host synchronisation.  workspace: tv_attn_branch_workspace_bytes(), 16-byte
+ * aligned. */
+size_t tv_attn_branch_workspace_bytes(int branches, int nheads_q, int nheads_kv, int prefix_len, int suffix_cap);
+int tv_attn_branch_fwd(const void* q, const void* k_prefix, const void* v_prefix, const void* k_suffix,
+                       const void* v_suffix, void* o, void* lse, int branches, int prefix_len, int suffix_cap,
+                       const int* seqlens_suffix, int nheads_q, int nheads_kv, int headdim, int64_t q_stride_b,
+                       int64_t q_stride_h, int64_t kp_stride_l, int64_t kp_stride_h, int64_t vp_stride_l,
+                       int64_t vp_stride_h, int64_t ks_stride_b, int64_t ks_stride_l, int64_t ks_stride_h,
+                       int64_t vs_stride_b, int64_t vs_stride_l, int64_t vs_stride_h, int64_t o_stride_b,
+                       int64_t o_stride_h, float softmax_scale, int dtype, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* launches of tv_attn_branch_fwd by this process so far (tests: a call did not fall back) */
+int tv_attn_branch_calls(void);
+
 /* ------------------------------------------------------------------------
  * T2  pdrop "attn" ranking.  Replaces modeling_nano.py:1822-1857,:1914-1939
  * without the (L,L) mask: one query row (the last prompt token) against all

@@ -50,6 +50,9 @@ SIGNATURES = {
     "tv_attn_append_workspace_bytes": (_z, [_i] * 5),
     "tv_attn_append_fwd": (_i, [_p] * 5 + [_i, _i, _i, _p, _i, _i, _i] + [_l] * 12 + [_f, _i, _p, _z, _p]),
     "tv_attn_append_calls": (_i, []),
+    "tv_attn_branch_workspace_bytes": (_z, [_i] * 5),
+    "tv_attn_branch_fwd": (_i, [_p] * 7 + [_i, _i, _i, _p, _i, _i, _i] + [_l] * 14 + [_f, _i, _p, _z, _p]),
+    "tv_attn_branch_calls": (_i, []),
     "tv_gemm_bf16_fwd": (_i, [_p, _p, _p, _p, _l, _i, _i, _l, _l, _l, _i, _i, _p]),
     "tv_gemm_set_persist": (None, [_i, _i]),
     "tv_gemm_set_drip": (None, [_i]),

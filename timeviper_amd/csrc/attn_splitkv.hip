@@ -1,9 +1,11 @@
-// T3 (decode and continuation): a FEW query tokens per sequence against a long K / V cache, as one split-KV walk with two
+// T3 (decode, continuation, branches): a FEW query tokens against a long K / V cache, as one split-KV walk with three
 // instantiations:
 //   tv_attn_decode_fwd   ONE query token — the attention of a generate() step (modeling_nano.py:1198-1209 with q_len == 1;
 //                        the cache layout of HybridMambaAttentionDynamicCache, :205-360);
 //   tv_attn_append_fwd   the LAST T tokens of a sequence — the attention of a forward that continues a prefilled cache with
-//                        a few tokens (a follow-up question, a tool result, a draft to verify).
+//                        a few tokens (a follow-up question, a tool result, a draft to verify);
+//   tv_attn_branch_fwd   ONE query token of each of B branches that share ONE prefix (a prefilled video asked several
+//                        questions at once) and hold a short suffix each.
 //
 // The prefill kernel (attention.hip) gives a (batch, q-head) pair to one work-group: with one query row that is
 // Hq work-groups walking the whole cache one after the other (32 for Nemotron-Nano-9B: 1/8 of the chip, each streaming
@@ -35,6 +37,14 @@
 // the last step(s) of the last split only.  A column can therefore see NO key in a step, a wave or a split (T = Lk: token
 // 0 sees key 0 alone): running maxima of -inf are kept out of the exponents, and a result is empty where its sum is 0.
 // With one token every step holds a key of the range and wave 0 always has a step: the maxima are finite.
+//
+// What the branches add (BRANCH; the other two instantiations contain none of it): ONE launch holds two kinds of
+// work-group.  A PREFIX work-group is the continuation's with the B branches in the place of the T tokens — the columns of a
+// kv-head are its B * gq (branch c / gq, head c % gq) pairs, the prefix K / V is read once per kv-head and block of 16
+// columns, never per branch — and without the causal bound: every branch sees the whole prefix.  A SUFFIX work-group is
+// the decode step's: the gq heads of ONE branch over that branch's own n_b rows (device-side count, clamped to the
+// capacity; n_b = 0: no work-group runs and the merge skips the slot).  A (branch, q-head) owns nsplit prefix slots followed
+// by nsplit_s suffix slots; the merge kernel reduces the ones that hold keys.  Prefix_len >= 1, so a result is never empty.
 #include "ssd_common.hpp"
 
 namespace {
@@ -59,6 +69,8 @@ constexpr int AD_MAX_SPLIT = 256;
 constexpr size_t AD_SLOT_BYTES = (AD_D + 2) * sizeof(float);      // workspace of a (column, split): fp32 O, max, sum
 constexpr int AP_MAX_T = 64, AP_MAX_COLS = 128;      // continuation: T <= 64 query tokens, T * gq <= 128 columns
 
+constexpr int BR_MAX = 16, BR_SUFFIX_SPLIT_KEYS = 4 * AD_NW * AD_STEP, BR_MAX_SUFFIX_SPLIT = 16;
+
 struct DecArgs {
   const bf16_t *q, *k, *v;
   bf16_t* o;
@@ -67,6 +79,11 @@ struct DecArgs {
   int Lk, Hq, Hkv, gq, hblocks, nsplit, T, ncols;          // hblocks: blocks of 16 of the T * gq columns of a kv-head
   int64_t qsl, osl, qsb, qsh, ksb, ksl, ksh, vsb, vsl, vsh, osb, osh;       // (decode: T = 1, the token strides unused)
   float scale_log2;
+  // the branch step alone: DecArgs describes the PREFIX (k / v one sequence, Lk = prefix_len, T = branches, the token strides
+  // = the branch strides of q and o, nsplit / hblocks of the prefix walk, `seqlens` the SUFFIX counts), these the suffixes
+  const bf16_t *ks, *vs;                      // (B, cap, Hkv, D)
+  int cap, nsplit_s, nblk_p, hbq;             // suffix capacity and splits; prefix work-groups of the grid; blocks of 16 of gq
+  int64_t kssb, kssl, kssh, vssb, vssl, vssh;
 };
 
 // keys of a sequence and the keys per split (a multiple of the step), the same in both kernels
@@ -82,247 +99,64 @@ __device__ __forceinline__ int64_t slot_of(const DecArgs& a, int b, int tok, int
   return ((APPEND ? (int64_t)b * a.T + tok : (int64_t)b) * a.Hq + head) * a.nsplit;
 }
 
+// The work of a BRANCH work-group (block x, uniform): the prefix work-groups first, split fastest, then the suffix ones.
+struct BranchWork {
+  bool sfx;
+  int split, hk, hb, br, Lk, chunk;           // hb: block of 16 of the B * gq columns (prefix) / of the gq heads (suffix)
+};
+__device__ __forceinline__ BranchWork branch_work(const DecArgs& a, int x) {
+  BranchWork w;
+  w.sfx = x >= a.nblk_p;
+  if (!w.sfx) {
+    w.split = x % a.nsplit;
+    x /= a.nsplit;
+    w.hb = x % a.hblocks;
+    w.hk = x / a.hblocks;
+    w.br = 0;
+    w.Lk = a.Lk;
+    w.chunk = ((a.Lk + a.nsplit - 1) / a.nsplit + AD_STEP - 1) / AD_STEP * AD_STEP;
+  } else {
+    x -= a.nblk_p;
+    w.split = x % a.nsplit_s;
+    x /= a.nsplit_s;
+    w.hb = x % a.hbq;
+    x /= a.hbq;
+    w.hk = x % a.Hkv;
+    w.br = x / a.Hkv;
+    w.Lk = a.seqlens ? min(max(a.seqlens[w.br], 0), a.cap) : a.cap;
+    w.chunk = ((w.Lk + a.nsplit_s - 1) / a.nsplit_s + AD_STEP - 1) / AD_STEP * AD_STEP;
+  }
+  if (w.chunk == 0) w.chunk = AD_STEP;
+  return w;
+}
+
+// The walk kernels share one body, attn_splitkv_walk.inc (`a`, APPEND and BRANCH are what it reads): it loads its Q
+// fragments with ssdk::gload16_async and walks the keys behind hand-counted vmcnt waits, so none of them may use scratch.
 template <bool APPEND>
 __global__ __launch_bounds__(AD_NW * 64) void attn_splitkv_kernel(DecArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char ad_smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = lane & 15, g = lane >> 4;                 // MFMA column (q-head / key row / d column) and k-quarter
-  const int split = blockIdx.x, b = blockIdx.z;
-  const int hk = blockIdx.y / a.hblocks, hb = blockIdx.y % a.hblocks;
-  const int nh = min(16, (APPEND ? a.ncols : a.gq) - 16 * hb);        // columns of this block
-  const int col = 16 * hb + min(n, nh - 1);               // this lane's column of the kv-head: (token, head)
-  const int tok = APPEND ? col / a.gq : 0, head = hk * a.gq + (APPEND ? col % a.gq : col);
-  int Lk, chunk;
-  split_of(a, b, Lk, chunk);
-  const int r0 = split * chunk, r1 = min(Lk, r0 + chunk);
-  if (r0 >= r1) return;                                   // (the merge kernel skips the same splits)
-  const int nsteps = (r1 - r0 + AD_STEP - 1) / AD_STEP;
-  const int lim = APPEND ? Lk - a.T + tok - r0 : 0;       // APPEND: last key this lane's column sees, relative to r0
-  const int nst = nsteps > wave ? (nsteps - wave + AD_NW - 1) / AD_NW : 0;      // steps wave, wave + AD_NW, ...
+  constexpr bool BRANCH = false;
+#include "attn_splitkv_walk.inc"
+}
 
-  const unsigned lds0 = lds_addr_of(ad_smem);
-  const unsigned ring = lds0 + (unsigned)(wave * AD_NS * AD_STAGE);
-
-  // ---- Q^T fragments (B operand): lane (n, g) holds Q[column n][32 ks + 8 g .. + 7]; columns past the block are zeros
-  bf16x8 qf[4];
-  {
-    const bf16_t* qp = a.q + (int64_t)b * a.qsb + (APPEND ? (int64_t)tok * a.qsl : 0) + (int64_t)head * a.qsh + 8 * g;
-    u32x4 raw[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) raw[ks] = gload16_async(qp + 32 * ks);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      settle(raw[ks]);
-      const bf16x8 z = {};
-      qf[ks] = n < nh ? __builtin_bit_cast(bf16x8, raw[ks]) : z;
-    }
-  }
-
-  // ---- K rows (A operand of S^T): tile G row m = key kb + 8 (m >> 2) + 4 G + (m & 3), so that the accumulator rows
-  // 4 g + i of tiles 0 / 1 are keys kb + 8 g + i and kb + 8 g + 4 + i: slots 0..7 of P's fragment for k-quarter g
-  const bf16_t* kg = a.k + (int64_t)b * a.ksb + (int64_t)hk * a.ksh + (int64_t)r0 * a.ksl;
-  const bf16_t* vg = a.v + (int64_t)b * a.vsb + (int64_t)hk * a.vsh + (int64_t)r0 * a.vsl;
-  const int last = r1 - 1 - r0;                            // last key of the range, relative to r0
-  // ---- copies: instruction i8 of a tile, lane l -> row 4 i8 + (l >> 4), physical 16-byte chunk l & 15, holding logical
-  // chunk (l & 15) ^ f(row):  K: f = (row & 3) | ((row >> 1) & 12) (distinct over the 16 rows {0..3, 8..11, 16..19, 24..27} (+ 4)
-  // that the 16 lanes of a ds_read_b128 group touch);
-  // V: f = 2 ((row & 3) | ((row >> 1) & 4)) (the 32 lanes of one half of a transposing read — rows 8 kq + q4, kq in a
-  // pair, 8-byte pieces p4 of the 32 bytes of d-tile ct — touch every bank once)
-  const int crow = lane >> 4;
-  const unsigned vchunk = (unsigned)((lane & 15) ^ (2 * (lane >> 4)));
-
-  auto issue = [&](int i, int S) __attribute__((always_inline)) {
-    const int kb = AD_STEP * (wave + AD_NW * i);           // relative to r0; rows past the range repeat its last key
-    const void* kbp = uniform_ptr(kg);
-    const void* vbp = uniform_ptr(vg);
-    const unsigned dst = ring + (unsigned)(S * AD_STAGE);
-#pragma unroll
-    for (int i8 = 0; i8 < 8; ++i8) {
-      const int row = 4 * i8 + crow, key = min(kb + row, last);
-      const unsigned ch = (unsigned)((lane & 15) ^ ((row & 3) | ((row >> 1) & 12)));
-      glds16(kbp, (unsigned)key * (unsigned)(a.ksl * 2) + ch * 16u, dst + (unsigned)(i8 * 1024));
-    }
-#pragma unroll
-    for (int i8 = 0; i8 < 8; ++i8) {
-      const int key = min(kb + 4 * i8 + crow, last);
-      const unsigned ch = vchunk ^ (unsigned)(8 * ((i8 >> 1) & 1));
-      glds16(vbp, (unsigned)key * (unsigned)(a.vsl * 2) + ch * 16u, dst + (unsigned)(AD_TILE + i8 * 1024));
-    }
-  };
-  // K fragment reads: lane (m = n, kq = g), tile G, k-step ks: row 8 (m >> 2) + 4 G + (m & 3), logical chunk 4 ks + kq
-  const int krow = 8 * (n >> 2) + (n & 3);
-  unsigned k_rd[2];
-#pragma unroll
-  for (int G = 0; G < 2; ++G) {
-    const int row = krow + 4 * G;
-    k_rd[G] = (unsigned)(row * AD_ROWB + ((g ^ ((row & 3) | ((row >> 1) & 12))) << 4));
-  }
-
-  // transposing reads: lane (lc = n, kq = g) gets keys 8 kq + 0..7 of d column 16 ct + lc (two reads: rows 8 kq + q4 and + 4)
-  const int q4 = n >> 2, p4 = n & 3;
-  const unsigned tr_base = (unsigned)((8 * g + q4) * AD_ROWB + 16 * (p4 >> 1) + 8 * (p4 & 1)) | (unsigned)((q4 | (4 * (g & 1))) << 5);
-
-  f32x4 oacc[8];
-#pragma unroll
-  for (int ct = 0; ct < 8; ++ct) oacc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m_run = -INFINITY, l_run = 0.f;
-
-  typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-  auto compute = [&](int i, int S) __attribute__((always_inline)) {
-    const int kb = AD_STEP * (wave + AD_NW * i);
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(AD_OPS * (AD_NS - 1)) : "memory");     // the younger steps stay in flight
-    const unsigned stage = ring + (unsigned)(S * AD_STAGE);
-    f32x4 sacc[2];
-#pragma unroll
-    for (int G = 0; G < 2; ++G) {
-      sacc[G] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        // (4 ks + g) ^ f = 4 ks ^ (g ^ f) for f < 16: the k-step flips bits 2..3 of the physical chunk
-        const bf16x8 kf = *(lds_bf16x8*)(size_t)(stage + (k_rd[G] ^ (unsigned)(ks << 6)));
-        sacc[G] = mfma16(kf, qf[ks], sacc[G]);
-      }
-    }
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int G = 0; G < 2; ++G)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool ok = kb + 8 * g + 4 * G + j <= (APPEND ? min(last, lim) : last);
-        sacc[G][j] = ok ? sacc[G][j] * a.scale_log2 : -INFINITY;
-        tmax = fmaxf(tmax, sacc[G][j]);
-      }
-    tmax = xor32_max(xor16_max(tmax));
-    const float m_new = fmaxf(m_run, tmax);                // APPEND: -inf while the column has seen no key
-    const float m_ref = APPEND && m_new == -INFINITY ? 0.f : m_new;
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_ref);
-    float ps = 0.f;
-    bf16x8 pf;
-#pragma unroll
-    for (int G = 0; G < 2; ++G)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float p = __builtin_amdgcn_exp2f(sacc[G][j] - m_ref);
-        ps += p;
-        pf[4 * G + j] = from_f32<bf16_t>(p);
-      }
-    l_run = l_run * alpha + ps;
-    if (__builtin_amdgcn_ballot_w64(m_new > m_run)) {
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct) oacc[ct] *= alpha;
-    }
-    m_run = m_new;
-    const unsigned st = stage + (unsigned)AD_TILE;
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) {
-      const unsigned p = st + (tr_base ^ (unsigned)(ct << 5));
-      const bf16x8 vf = cat4(__builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)(size_t)p),
-                             __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)(size_t)(p + 4 * AD_ROWB)));
-      oacc[ct] = mfma16(vf, pf, oacc[ct]);
-    }
-  };
-
-  {
-#pragma unroll
-    for (int j = 0; j < AD_NS - 1; ++j) issue(j, j);
-    int S = 0;                                             // ring stage of step i
-    for (int i = 0; i < nst; ++i) {
-      const int Sn = S == 0 ? AD_NS - 1 : S - 1;           // (S + AD_NS - 1) % AD_NS: the stage step i - 1 has left
-      issue(i + AD_NS - 1, Sn);
-      compute(i, S);
-      S = S == AD_NS - 1 ? 0 : S + 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (copies of steps past the range)
-  }
-
-  // ---- merge the waves: [wave][ct * 4 + i][lane] partial O, per-lane max / sum (sum over the head's 4 lanes first);
-  // the arrays lie over the ring, which every wave has left
-  l_run = xor32_sum(xor16_sum(l_run));
-  __syncthreads();
-  float* mo = (float*)ad_smem;
-  float* mm = mo + AD_NW * 32 * 64;
-  float* ml = mm + AD_NW * 64;
-#pragma unroll
-  for (int ct = 0; ct < 8; ++ct)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) mo[(wave * 32 + ct * 4 + j) * 64 + lane] = oacc[ct][j];
-  mm[wave * 64 + lane] = m_run;
-  ml[wave * 64 + lane] = l_run;
-  __syncthreads();
-  float m_tot = -INFINITY;
-#pragma unroll
-  for (int w = 0; w < AD_NW; ++w) m_tot = fmaxf(m_tot, mm[w * 64 + lane]);       // APPEND: -inf if the column sees no key of the split
-  const float m_ref = APPEND && m_tot == -INFINITY ? 0.f : m_tot;
-  float sc[AD_NW], l_tot = 0.f;
-#pragma unroll
-  for (int w = 0; w < AD_NW; ++w) {
-    sc[w] = __builtin_amdgcn_exp2f(mm[w * 64 + lane] - m_ref);                    // exp2(-inf) = 0 for idle waves
-    l_tot += sc[w] * ml[w * 64 + lane];
-  }
-  if (n < nh) {
-    const int64_t slot = slot_of<APPEND>(a, b, tok, head) + split;
-    for (int ct = wave; ct < 8; ct += AD_NW) {
-      f32x4 r = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int w = 0; w < AD_NW; ++w)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) r[j] += sc[w] * mo[(w * 32 + ct * 4 + j) * 64 + lane];
-      *(f32x4*)(a.part_o + slot * AD_D + 16 * ct + 4 * g) = r;     // O^T rows d = 16 ct + 4 g + j of column n
-    }
-    if (wave == 0 && g == 0) {
-      a.part_ml[slot * 2] = m_tot;
-      a.part_ml[slot * 2 + 1] = l_tot;
-    }
-  }
+__global__ __launch_bounds__(AD_NW * 64) void attn_branch_kernel(DecArgs a) {
+  constexpr bool APPEND = false, BRANCH = true;
+#include "attn_splitkv_walk.inc"
 }
 
 // o[b][tok][h][d] = sum_s 2^(m_s - M) O_s[d] / sum_s 2^(m_s - M) l_s over the splits that hold keys; 128 threads,
 // grid (Hq, batch), or (T * Hq, batch) with block x = token * Hq + head for the continuation.
 // One pass with a running maximum, the loads of 8 splits issued before their first use (a split at a time the kernel was
 // 32 dependent round trips to L2: 12 us for 1 MB).
+// BRANCH: grid (B * Hq), block x = branch * Hq + head; the prefix slots that hold keys, then the suffix ones.
 template <bool APPEND>
 __global__ __launch_bounds__(AD_D) void attn_splitkv_merge_kernel(DecArgs a) {
-  constexpr int U = 8;
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  const int tok = APPEND ? blockIdx.x / a.Hq : 0, h = APPEND ? blockIdx.x % a.Hq : blockIdx.x;
-  const int b = blockIdx.y, d = threadIdx.x;
-  int Lk, chunk;
-  split_of(a, b, Lk, chunk);
-  const int nvalid = (Lk + chunk - 1) / chunk;
-  const int64_t slot0 = slot_of<APPEND>(a, b, tok, h);
-  float M = -INFINITY, L = 0.f, O = 0.f;
-  for (int s0 = 0; s0 < nvalid; s0 += U) {
-    f32x2 ml[U];
-    float o[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int sidx = min(s0 + u, nvalid - 1);        // (past the end: the last split again, weighted 0 below)
-      ml[u] = *(const f32x2*)(a.part_ml + (slot0 + sidx) * 2);
-      o[u] = a.part_o[(slot0 + sidx) * AD_D + d];
-    }
-    float mb = M;
-#pragma unroll
-    for (int u = 0; u < U; ++u) mb = s0 + u < nvalid ? fmaxf(mb, ml[u][0]) : mb;
-    const float mr = APPEND && mb == -INFINITY ? 0.f : mb;       // (APPEND: no split so far holds a key this column sees)
-    const float sc = __builtin_amdgcn_exp2f(M - mr);   // (M = -inf: 0)
-    L *= sc;
-    O *= sc;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const float w = s0 + u < nvalid ? __builtin_amdgcn_exp2f(ml[u][0] - mr) : 0.f;
-      L = fmaf(w, ml[u][1], L);
-      O = fmaf(w, o[u], O);
-    }
-    M = mb;
-  }
-  // (the two tests agree on finite partials; a NaN in them reaches a decode result and not a continuation's)
-  const bool any = APPEND ? L > 0.f : nvalid > 0;
-  a.o[(int64_t)b * a.osb + (APPEND ? (int64_t)tok * a.osl : 0) + (int64_t)h * a.osh + d] = from_f32<bf16_t>(any ? O / L : 0.f);
-  if (a.lse && d == 0)          // (B, Hq), continuation (B, Hq, T)
-    a.lse[APPEND ? ((int64_t)b * a.Hq + h) * a.T + tok : (int64_t)b * a.Hq + h] =
-        any ? (M + __log2f(L)) * 0.6931471805599453f : -INFINITY;
+  constexpr bool BRANCH = false;
+#include "attn_splitkv_merge.inc"
+}
+
+__global__ __launch_bounds__(AD_D) void attn_branch_merge_kernel(DecArgs a) {
+  constexpr bool APPEND = false, BRANCH = true;
+#include "attn_splitkv_merge.inc"
 }
 
 int pick_splits(int batch, int nheads_kv, int hblocks, int seqlen_k) {
@@ -377,7 +211,7 @@ int splitkv_fwd(const char* name, const void* q, const void* k, const void* v, v
   const size_t need = slots * AD_SLOT_BYTES;
   TV_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0,
                "%s: workspace of %zu bytes (16-byte aligned) needed, got %zu", name, need, workspace_bytes);
-  DecArgs a;
+  DecArgs a = {};
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o; a.lse = (float*)lse;
   a.part_o = (float*)workspace;
   a.part_ml = a.part_o + slots * AD_D;
@@ -401,7 +235,98 @@ int splitkv_fwd(const char* name, const void* q, const void* k, const void* v, v
   TV_LAUNCH_CHECK();
 }
 
+// ---- the branch step
+int g_branch_calls = 0;
+
+int branch_suffix_splits(int suffix_cap) {
+  const int want = (suffix_cap + BR_SUFFIX_SPLIT_KEYS - 1) / BR_SUFFIX_SPLIT_KEYS;
+  return want < 1 ? 1 : want > BR_MAX_SUFFIX_SPLIT ? BR_MAX_SUFFIX_SPLIT : want;
+}
+
+// in the kernel's range: B <= 16 branches, B * gq <= 128 columns
+bool branch_in_range(int branches, int nheads_q, int nheads_kv) {
+  return branches <= BR_MAX && branches * (nheads_q / nheads_kv) <= AP_MAX_COLS;
+}
+
 }  // namespace
+
+extern "C" size_t tv_attn_branch_workspace_bytes(int branches, int nheads_q, int nheads_kv, int prefix_len, int suffix_cap) {
+  if (branches <= 0 || nheads_q <= 0 || nheads_kv <= 0 || nheads_q % nheads_kv || prefix_len < 1 || suffix_cap < 0 ||
+      !branch_in_range(branches, nheads_q, nheads_kv))
+    return 0;
+  const int hblocks = (branches * (nheads_q / nheads_kv) + 15) / 16;
+  return (size_t)branches * nheads_q * (pick_splits(1, nheads_kv, hblocks, prefix_len) + branch_suffix_splits(suffix_cap)) *
+         AD_SLOT_BYTES;
+}
+
+extern "C" int tv_attn_branch_calls(void) { return g_branch_calls; }
+
+extern "C" int tv_attn_branch_fwd(const void* q, const void* k_prefix, const void* v_prefix, const void* k_suffix,
+                                  const void* v_suffix, void* o, void* lse, int branches, int prefix_len, int suffix_cap,
+                                  const int* seqlens_suffix, int nheads_q, int nheads_kv, int headdim, int64_t q_stride_b,
+                                  int64_t q_stride_h, int64_t kp_stride_l, int64_t kp_stride_h, int64_t vp_stride_l,
+                                  int64_t vp_stride_h, int64_t ks_stride_b, int64_t ks_stride_l, int64_t ks_stride_h,
+                                  int64_t vs_stride_b, int64_t vs_stride_l, int64_t vs_stride_h, int64_t o_stride_b,
+                                  int64_t o_stride_h, float softmax_scale, int dtype, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  const char* name = "attn_branch";
+  TV_CHECK_ARG(q && o && k_prefix && v_prefix && (suffix_cap == 0 || (k_suffix && v_suffix)), "%s: null pointer", name);
+  TV_CHECK_ARG(branches > 0 && prefix_len >= 1 && suffix_cap >= 0 && nheads_q > 0 && nheads_kv > 0 &&
+                   nheads_q % nheads_kv == 0 && softmax_scale > 0.f,
+               "%s: bad sizes or non-positive softmax scale (the shared prefix holds at least one key)", name);
+  if (dtype != TV_BF16) TV_UNSUPPORTED("%s: dtype must be bf16", name);
+  if (headdim != AD_D) TV_UNSUPPORTED("%s: headdim %d (this kernel: 128)", name, headdim);
+  const int gq = nheads_q / nheads_kv, ncols = branches * gq, hblocks = (ncols + 15) / 16, hbq = (gq + 15) / 16;
+  if (!branch_in_range(branches, nheads_q, nheads_kv))
+    TV_UNSUPPORTED("%s: %d branches x %d q-heads per kv-head (this kernel: <= %d branches, <= %d columns)", name, branches,
+                   gq, BR_MAX, AP_MAX_COLS);
+  const int64_t strides[] = {q_stride_b, q_stride_h, kp_stride_l, kp_stride_h, vp_stride_l, vp_stride_h,
+                             ks_stride_b, ks_stride_l, ks_stride_h, vs_stride_b, vs_stride_l, vs_stride_h};
+  for (int64_t s : strides)
+    if (s % 8) TV_UNSUPPORTED("%s: q/k/v strides must be multiples of 8 elements", name);
+  if (((uintptr_t)q & 15) || ((uintptr_t)k_prefix & 15) || ((uintptr_t)v_prefix & 15) || ((uintptr_t)k_suffix & 15) ||
+      ((uintptr_t)v_suffix & 15))
+    TV_UNSUPPORTED("%s: q/k/v must be 16-byte aligned", name);
+  if (kp_stride_l < AD_D || vp_stride_l < AD_D || (suffix_cap > 0 && (ks_stride_l < AD_D || vs_stride_l < AD_D)))
+    TV_UNSUPPORTED("%s: k/v rows must not overlap", name);
+  const int nsplit = pick_splits(1, nheads_kv, hblocks, prefix_len), nsplit_s = branch_suffix_splits(suffix_cap);
+  // K and V rows are addressed with 32-bit byte offsets from the first key of a split
+  const int64_t rows_p = (int64_t)prefix_len / nsplit + 2 * AD_STEP, rows_s = (int64_t)suffix_cap / nsplit_s + 2 * AD_STEP;
+  if (rows_p * kp_stride_l * 2 >= (1ll << 31) || rows_p * vp_stride_l * 2 >= (1ll << 31) ||
+      rows_s * ks_stride_l * 2 >= (1ll << 31) || rows_s * vs_stride_l * 2 >= (1ll << 31))
+    TV_UNSUPPORTED("%s: k / v row stride too large for a split", name);
+  const size_t slots = (size_t)branches * nheads_q * (nsplit + nsplit_s);
+  const size_t need = slots * AD_SLOT_BYTES;
+  TV_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0,
+               "%s: workspace of %zu bytes (16-byte aligned) needed, got %zu", name, need, workspace_bytes);
+  DecArgs a = {};
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k_prefix; a.v = (const bf16_t*)v_prefix; a.o = (bf16_t*)o; a.lse = (float*)lse;
+  a.part_o = (float*)workspace;
+  a.part_ml = a.part_o + slots * AD_D;
+  a.seqlens = seqlens_suffix;
+  a.Lk = prefix_len; a.Hq = nheads_q; a.Hkv = nheads_kv; a.gq = gq; a.hblocks = hblocks; a.nsplit = nsplit;
+  a.T = branches; a.ncols = ncols; a.qsl = q_stride_b; a.osl = o_stride_b;
+  a.qsb = 0; a.qsh = q_stride_h; a.ksb = 0; a.ksl = kp_stride_l; a.ksh = kp_stride_h;
+  a.vsb = 0; a.vsl = vp_stride_l; a.vsh = vp_stride_h; a.osb = 0; a.osh = o_stride_h;
+  a.scale_log2 = softmax_scale * 1.4426950408889634f;
+  a.ks = (const bf16_t*)k_suffix; a.vs = (const bf16_t*)v_suffix;
+  a.cap = suffix_cap; a.nsplit_s = nsplit_s; a.nblk_p = nsplit * nheads_kv * hblocks; a.hbq = hbq;
+  a.kssb = ks_stride_b; a.kssl = ks_stride_l; a.kssh = ks_stride_h;
+  a.vssb = vs_stride_b; a.vssl = vs_stride_l; a.vssh = vs_stride_h;
+  hipStream_t st = (hipStream_t)stream;
+  static const hipError_t attr = hipFuncSetAttribute((const void*)attn_branch_kernel,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, AD_LDS);
+  if (attr != hipSuccess) {
+    tv_set_error("%s: cannot reserve %d bytes of LDS: %s", name, AD_LDS, hipGetErrorString(attr));
+    return TV_ERR_LAUNCH;
+  }
+  ++g_branch_calls;
+  // (suffix work-groups of a branch with no rows, or of a capacity of 0, leave at once)
+  const unsigned nblk = (unsigned)(a.nblk_p + (suffix_cap > 0 ? branches * nheads_kv * hbq * nsplit_s : 0));
+  attn_branch_kernel<<<dim3(nblk), AD_NW * 64, AD_LDS, st>>>(a);
+  attn_branch_merge_kernel<<<dim3((unsigned)(branches * nheads_q)), AD_D, 0, st>>>(a);
+  TV_LAUNCH_CHECK();
+}
 
 extern "C" size_t tv_attn_decode_workspace_bytes(int batch, int nheads_q, int nheads_kv, int seqlen_k) {
   return workspace_bytes(batch, 1, nheads_q, nheads_kv, seqlen_k);

@@ -782,16 +782,17 @@ def _rows_on_library(T: int, N: int, K: int) -> bool:
 
 
 def linear_rows_takes(x: torch.Tensor, weight: torch.Tensor) -> bool:
-    """Shapes tv_linear_rows_bf16_fwd is written for: the 1..16 token rows of ONE sequence, bf16 (1, T, K) or (T, K) with
-    dense rows, against a bf16 (N, K) weight."""
-    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[0] != 1):
+    """Shapes tv_linear_rows_bf16_fwd is written for: the 1..16 token rows of ONE sequence, bf16 (1, T, K) or (T, K), or ONE
+    token of each of 1..16 sequences, (B, 1, K), with dense rows, against a bf16 (N, K) weight."""
+    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[0] != 1 and x.shape[1] != 1):
         return False
     K = x.shape[-1]
+    rdim = 0 if x.dim() == 3 and x.shape[0] != 1 else -2         # the dimension the rows run along
     return (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and weight.dim() == 2
-            and 1 <= x.shape[-2] <= 16 and K % 8 == 0 and K >= 8 and weight.shape[1] == K and x.stride(-1) == 1
-            and x.stride(-2) % 8 == 0 and weight.stride(1) == 1 and weight.stride(0) % 8 == 0
+            and 1 <= x.shape[rdim] <= 16 and K % 8 == 0 and K >= 8 and weight.shape[1] == K and x.stride(-1) == 1
+            and x.stride(rdim) % 8 == 0 and weight.stride(1) == 1 and weight.stride(0) % 8 == 0
             and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
-            and not _rows_on_library(x.shape[-2], weight.shape[0], K))
+            and not _rows_on_library(x.shape[rdim], weight.shape[0], K))
 
 
 def linear_rows_fused(x, weight, bias=None, prologue=GEMV_NONE, delta=None, sum_out=None, norm_weight=None, eps=0.0,
@@ -1119,4 +1120,70 @@ def flash_attn_append(q, k, v, seqlens_k=None, softmax_scale=None, return_lse=Fa
     if st == -2 and seqlens_k is None:      # TV_ERR_UNSUPPORTED (e.g. a row stride too large for a split)
         return flash_attn_func(q, k, v, softmax_scale=softmax_scale, causal=True, return_lse=return_lse)
     check(st, "tv_attn_append_fwd")
+    return (o, lse) if return_lse else o
+
+
+def flash_attn_branch_calls() -> int:
+    """Launches of tv_attn_branch_fwd by this process (tests: a branched step's attention did not fall back)."""
+    return int(_capi.lib().tv_attn_branch_calls())
+
+
+def _branch_fallback(q, k_prefix, v_prefix, k_suffix, v_suffix, seqlens_suffix, softmax_scale, return_lse):
+    """Branch by branch on the concatenated keys (the prefix COPIED per branch) through `flash_attn_func` with one query row
+    (the decode kernel where it takes the shape).  Reads the suffix lengths on the host."""
+    B, _, Hq, D = q.shape
+    cap = k_suffix.shape[1]
+    ns = [cap] * B if seqlens_suffix is None else [min(max(int(n), 0), cap) for n in seqlens_suffix.tolist()]
+    outs, lses = [], []
+    for b in range(B):
+        k = torch.cat([k_prefix, k_suffix[b:b + 1, :ns[b]]], dim=1)
+        v = torch.cat([v_prefix, v_suffix[b:b + 1, :ns[b]]], dim=1)
+        r = flash_attn_func(q[b:b + 1], k, v, softmax_scale=softmax_scale, causal=False, return_lse=True)
+        outs.append(r[0])
+        lses.append(r[1].reshape(1, Hq, 1))
+    o = torch.cat(outs, dim=0)
+    return (o, torch.cat(lses, dim=0)) if return_lse else o
+
+
+def flash_attn_branch(q, k_prefix, v_prefix, k_suffix, v_suffix, seqlens_suffix=None, softmax_scale=None,
+                      return_lse=False):
+    """One query token of each of B branches that share one prefix: q (B, 1, Hq, 128) bf16, k_prefix / v_prefix
+    (1, Lp, Hkv, 128) — ONE sequence, seen whole by every branch, Lp >= 1 — and k_suffix / v_suffix (B, cap, Hkv, 128), of
+    which branch b sees its own rows [0, n_b) -> (B, 1, Hq, 128) (and lse (B, Hq, 1)).  `seqlens_suffix`: int32 tensor (B,)
+    ON THE GPU with n_b (clamped to [0, cap]) — the form a captured step replays with; None: all cap rows.  The prefix is
+    read once per kv-head and block of 16 (branch, head) columns (tv_attn_branch_fwd), not once per branch.  Shapes the
+    kernel does not take (B > 16, B * Hq / Hkv > 128, other head dims / dtypes) run branch by branch on the concatenated
+    keys: the same results, not the same speed."""
+    _gpu(q, k_prefix, v_prefix, k_suffix, v_suffix, seqlens_suffix)
+    B, Lq, Hq, D = q.shape
+    Lp, Hkv = k_prefix.shape[1], k_prefix.shape[2]
+    cap = k_suffix.shape[1]
+    if Lq != 1 or k_prefix.shape[0] != 1 or v_prefix.shape != k_prefix.shape or Lp < 1:
+        raise TimeViperHipError("flash_attn_branch: one query token per branch, ONE prefix sequence of at least one key")
+    if k_suffix.shape != (B, cap, Hkv, D) or v_suffix.shape != k_suffix.shape:
+        raise TimeViperHipError("flash_attn_branch: k_suffix / v_suffix must be (B, cap, Hkv, D)")
+    if seqlens_suffix is not None and (seqlens_suffix.dtype != torch.int32 or seqlens_suffix.numel() != B
+                                       or not seqlens_suffix.is_contiguous()):
+        raise TimeViperHipError("flash_attn_branch: seqlens_suffix must be a contiguous int32 tensor of B entries")
+    fix = lambda t: t if t.stride(-1) == 1 else t.contiguous()
+    q, k_prefix, v_prefix, k_suffix, v_suffix = (fix(t) for t in (q, k_prefix, v_prefix, k_suffix, v_suffix))
+    ts = (q, k_prefix, v_prefix, k_suffix, v_suffix)
+    takes = (q.dtype == torch.bfloat16 and D == 128 and B <= 16 and B * (Hq // Hkv) <= 128
+             and all(s % 8 == 0 for t in ts for s in t.stride()[:3]) and all(t.data_ptr() % 16 == 0 for t in ts))
+    scale = 1.0 / math.sqrt(D) if softmax_scale is None else float(softmax_scale)
+    if not takes:
+        return _branch_fallback(q, k_prefix, v_prefix, k_suffix, v_suffix, seqlens_suffix, scale, return_lse)
+    o = torch.empty((B, 1, Hq, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, Hq, 1), dtype=torch.float32, device=q.device) if return_lse else None
+    lib = _capi.lib()
+    ws = torch.empty((max(int(lib.tv_attn_branch_workspace_bytes(B, Hq, Hkv, Lp, cap)), 16),), dtype=torch.uint8,
+                     device=q.device)
+    st = lib.tv_attn_branch_fwd(
+        _p(q), _p(k_prefix), _p(v_prefix), _p(k_suffix), _p(v_suffix), _p(o), _p(lse), B, Lp, cap, _p(seqlens_suffix),
+        Hq, Hkv, D, q.stride(0), q.stride(2), k_prefix.stride(1), k_prefix.stride(2), v_prefix.stride(1),
+        v_prefix.stride(2), k_suffix.stride(0), k_suffix.stride(1), k_suffix.stride(2), v_suffix.stride(0),
+        v_suffix.stride(1), v_suffix.stride(2), o.stride(0), o.stride(2), scale, _dt(q), _p(ws), ws.numel(), _stream())
+    if st == -2:        # TV_ERR_UNSUPPORTED (e.g. a row stride too large for a split)
+        return _branch_fallback(q, k_prefix, v_prefix, k_suffix, v_suffix, seqlens_suffix, scale, return_lse)
+    check(st, "tv_attn_branch_fwd")
     return (o, lse) if return_lse else o

@@ -459,6 +459,113 @@ class GenericTimeViperVLM(nn.Module):
                      capture_error=None if stepper.capture_error is None else repr(stepper.capture_error))
         return new_tokens, fed
 
+    def _branch_scope(self, cache, n_branches: int) -> bool:
+        """Whether `generate_branches` decodes its questions in lockstep (llm/branch.py): the Nemotron-H hybrid with its
+        hybrid cache, 1..16 branches, no fp8 attention; on the GPU bf16, attention head_dim 128 and
+        branches x Hq / Hkv <= 128 columns (tv_attn_branch_fwd).  Anything else runs question by question on clones."""
+        from .llm.branch import MAX_BRANCHES
+        from .llm.nano import HybridMambaAttentionDynamicCache, NemotronHForCausalLM
+        from .. import kernels as K
+        llm = self.llm_backbone.llm
+        if (not isinstance(llm, NemotronHForCausalLM) or not isinstance(cache, HybridMambaAttentionDynamicCache)
+                or not cache.attention_layers or not 1 <= n_branches <= MAX_BRANCHES or K._ATTN_FP8["on"]
+                or llm.dtype not in (torch.bfloat16, torch.float32)):
+            return False
+        if self.device.type == "cuda":
+            cfg = llm.config
+            if (llm.dtype != torch.bfloat16 or cache.key_cache[cache.attention_layers[0]].shape[-1] != 128
+                    or n_branches * (cfg.num_attention_heads // cfg.num_key_value_heads) > 128):
+                return False
+        return True
+
+    @torch.inference_mode()
+    def generate_branches(self, questions, past_key_values=None, max_new_tokens: int = 128, eos_token_id=None,
+                          answer_prompt: Optional[str] = None, return_ids: bool = False) -> list:
+        """Several questions about ONE prefilled video: `questions` is a list of 1..16 id tensors (1, T_b), text only,
+        `past_key_values` the cache a `generate(..., return_past_key_values=True)` (or a prefill forward) left.  Result b
+        is what `generate(questions[b], past_key_values=cache.clone(), ...)` with the same arguments returns; the cache
+        itself is not modified.
+
+        The questions are decoded in LOCKSTEP on `cache.branch(B)`: every step feeds ONE token per branch — the cache's
+        pending ids, then the branch's question, then the tokenised `answer_prompt`, then the branch's own greedy tokens —
+        as the B rows of one forward: the weights are read once per step for all branches, the K / V of the video is
+        shared and read once per step and attention layer.  All branches hold the same number of rows at all times; a
+        branch with a short question starts answering earlier, a finished one (end-of-sequence id, `max_new_tokens`)
+        rides along as a padding row until the last one is done.  The step is one captured graph where plain `generate`
+        would capture its step (`TV_DECODE_GRAPH`).  Out of scope (`_branch_scope`: Qwen2, fp32 on the GPU, more than
+        16 questions, ...) the questions run one after the other on clones.  `last_generate_stats`: branched, branches,
+        steps (forwards), graphed."""
+        cache = past_key_values
+        if cache is None:
+            raise ValueError("generate_branches: past_key_values (the prefilled cache the questions are about) is required")
+        questions = [q.view(1, -1) for q in questions]
+        B, max_new_tokens = len(questions), int(max_new_tokens)
+        if B < 1 or any(q.numel() == 0 for q in questions):
+            raise ValueError("generate_branches: at least one question, each of at least one id")
+        if not self._branch_scope(cache, B):
+            results, steps, graphed = [], 0, False
+            for q in questions:
+                results.append(self.generate(q, past_key_values=cache.clone(), max_new_tokens=max_new_tokens,
+                                             eos_token_id=eos_token_id, answer_prompt=answer_prompt, return_ids=return_ids))
+                steps += self.last_generate_stats["steps"]
+                graphed = graphed or bool(self.last_generate_stats["graphed"])
+            self.last_generate_stats = {"branched": False, "branches": B, "steps": steps, "graphed": graphed}
+            return results
+        eos = self.eos_token_ids_to_use if eos_token_id is None else eos_token_id
+        eos = set(int(t) for t in (eos if isinstance(eos, (list, tuple)) else [eos]))
+        if getattr(cache, "get_seq_length", None) and cache.get_seq_length() == 0:
+            raise ValueError("generate_branches: the cache holds no prefill")
+        tail: List[int] = []
+        if answer_prompt:
+            tail = self.llm_backbone.tokenizer(answer_prompt, add_special_tokens=False,
+                                               return_tensors="pt").input_ids.reshape(-1).tolist()
+        pending = getattr(cache, "pending_ids", None)
+        head = [] if pending is None else pending.reshape(-1).tolist()
+        feeds = [[int(t) for t in head + q.reshape(-1).tolist() + tail] for q in questions]
+        n_steps = max(len(f) for f in feeds) + max(max_new_tokens - 1, 0)       # (the last emitted token is not fed)
+        bs = cache.branch(B, suffix_cap=n_steps)
+        bs.begin_static_decode(n_steps)
+        pdargs = getattr(bs, "pdrop_args", self.pdrop_args if self.use_pdrop else None)      # (as `generate` reads the cache's)
+        host_pos = torch.ones(1, dtype=torch.long)              # "not the prefill" for the mixers' host-side branch
+        dev_pos = torch.ones((B, 1), dtype=torch.long, device=self.device)
+
+        def step_fn(ids):
+            return self.llm_backbone(input_ids=ids, past_key_values=bs, use_cache=True, cache_position=host_pos,
+                                     position_ids=dev_pos, train_pdrop_args=pdargs).logits
+        stepper = None
+        if (os.environ.get("TV_DECODE_GRAPH", "1") != "0" and self.device.type == "cuda" and max_new_tokens >= 8
+                and self.dtype == torch.bfloat16):
+            from .llm.decode_graph import GraphedDecodeStep
+            stepper = GraphedDecodeStep(step_fn, bs, B, self.device)
+        new_tokens: List[List[int]] = [[] for _ in range(B)]
+        done = [max_new_tokens <= 0] * B
+        steps = 0
+        while not all(done):
+            # branch b feeds its prompt, then its own last token; a finished branch rides along as a padding row
+            row = [f[steps] if steps < len(f) else (t[-1] if t else 0) for f, t in zip(feeds, new_tokens)]
+            ids = torch.tensor(row, dtype=torch.long, device=self.device).view(B, 1)
+            if stepper is not None:
+                nxt = stepper.step(ids)
+            else:
+                nxt = step_fn(ids)[:, -1].argmax(-1)
+                bs.advance_static_device()
+            steps += 1
+            nxt = nxt.reshape(-1).tolist()
+            for b in range(B):
+                if done[b] or steps < len(feeds[b]):            # (still inside its prompt: the logits are not its answer's)
+                    continue
+                new_tokens[b].append(int(nxt[b]))
+                done[b] = nxt[b] in eos or len(new_tokens[b]) >= max_new_tokens
+        self.last_generate_stats = {"branched": True, "branches": B, "steps": steps,
+                                    "graphed": stepper is not None and stepper.graph is not None}
+        tokenizer = self.llm_backbone.tokenizer
+        results = []
+        for t in new_tokens:
+            ids = torch.tensor([t], device=self.device)
+            results.append(ids if return_ids or not hasattr(tokenizer, "decode")
+                           else tokenizer.decode(ids[0], skip_special_tokens=False).strip())
+        return results
+
     def _graphed_decode_step(self, cache, max_new_tokens, pdargs):
         """The decode step behind `generate` as a captured graph (llm/decode_graph.py) where the stack allows it: the
         Nemotron-H hybrid (no positional encoding), bf16, attention head_dim 128 (tv_attn_decode_fwd), on the GPU, and

@@ -305,6 +305,14 @@ class HybridMambaAttentionDynamicCache:
             new.pdrop_args = dict(self.pdrop_args)
         return new
 
+    def branch(self, n: int, suffix_cap: int = 256):
+        """n branches of this cache that are decoded together, one token per branch and step (llm/branch.py): K / V at
+        their current lengths are SHARED with the set as the prefix every branch sees (no copy), the conv / SSM states are
+        copied n times, every branch gets suffix buffers of `suffix_cap` rows.  This cache is not written by the set and
+        must not be appended to while the set is in use.  Raises in speculation mode or without a prefill."""
+        from .branch import BranchSet
+        return BranchSet(self, n, suffix_cap)
+
     # ---- speculation: T tokens per forward taken provisionally, the first k kept (see NemotronHMamba2Mixer._speculate)
     def begin_speculation(self, t_max: int, max_new_tokens: int):
         """Behind a prefill: from now on a forward of T <= t_max tokens leaves the conv / SSM states and the committed
@@ -494,15 +502,15 @@ def linear_route(x, cache=None, cache_position=None) -> Optional[str]:
     per call):
       "gemv"  tv_gemv_bf16_fwd — one token of 1..4 sequences, unless TV_DECODE_FUSED=0;
       "rows"  tv_linear_rows_bf16_fwd — 2..16 tokens of one sequence behind a prefill (a continuation, a speculative
-              step) under TV_ROWS_FUSED=1 (off by default until the step is measured faster on an MI355X, DESIGN.md
-              section 3);
+              step), or one token of 5..16 sequences behind one (a branched step), under TV_ROWS_FUSED=1 (off by default
+              until the step is measured faster on an MI355X, DESIGN.md section 3);
       None    torch.nn.Linear (library GEMM, same arithmetic)."""
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3 and not torch.is_grad_enabled()):
         return None
     B, T = x.shape[:2]
     if T == 1 and B <= 4:
         return "gemv" if os.environ.get("TV_DECODE_FUSED", "1") != "0" else None
-    if (B == 1 and 2 <= T <= 16 and os.environ.get("TV_ROWS_FUSED", ROWS_FUSED_DEFAULT) != "0"
+    if (((B == 1 and 2 <= T <= 16) or (T == 1 and 5 <= B <= 16)) and os.environ.get("TV_ROWS_FUSED", ROWS_FUSED_DEFAULT) != "0"
             and is_continuation(cache, cache_position)):
         return "rows"
     return None
@@ -756,9 +764,10 @@ class NemotronHMamba2Mixer(nn.Module):
         """A forward behind a prefill with the block's RMSNorm (+ residual add) inside in_proj and the gated norm inside
         out_proj: in_proj -> `_recur` -> out_proj (one token: 3 launches).  Returns (residual stream, mixer output)."""
         conv = None
-        if hidden.shape[1] == 1:
-            # one token (the gemv route): the conv update rides in the product's epilogue where the kernel offers it
-            # (width 4, SiLU, K < 8192)
+        if hidden.shape[1] == 1 and lin is K.gemv_fused:
+            # one token on the gemv route: the conv update rides in the product's epilogue where the kernel offers it
+            # (width 4, SiLU, K < 8192).  (One token of 5..16 sequences rides the rows kernel, which has no conv epilogue:
+            # `_decode` then runs the conv update as its own launch.)
             conv_state, w = cache_params.conv_states[self.layer_idx], self.conv1d.weight.squeeze(1)
             if (self.conv_kernel_size == 4 and self.activation in ("silu", "swish") and hidden.shape[-1] < 8192
                     and conv_state.dtype == hidden.dtype and conv_state.is_contiguous() and w.is_contiguous()):
@@ -834,6 +843,10 @@ class NemotronHAttention(nn.Module):
     def _attend(self, q, k, v, cache, continuation):
         """The new keys / values into the cache (if any) and the attention of the new queries over all of it."""
         q_len = q.shape[1]
+        if getattr(cache, "is_branch_set", False):
+            # one token of each branch of a shared prefix (llm/branch.py): the rows go into the branches' own suffix buffers,
+            # the prefix is read once for all of them
+            return K.flash_attn_branch(q, *cache.write(k, v, self.layer_idx))
         if continuation and getattr(cache, "speculating", False):
             return self._attend_provisional(q, k, v, cache)
         if cache is not None:
@@ -879,7 +892,7 @@ class NemotronHAttention(nn.Module):
         v = v.view(B, T, self.num_key_value_heads, self.head_dim)
         o = self._attend(q, k, v, cache, True).reshape(B, T, nq)
         # (one token: `_linear`, which asks gemv_takes for the shape; several: the rows kernel takes every shape)
-        return new_hidden, (_linear(self.o_proj, o, "gemv") if T == 1 else lin(o, self.o_proj.weight, None, K.GEMV_NONE))
+        return new_hidden, (_linear(self.o_proj, o, "gemv") if lin is K.gemv_fused else lin(o, self.o_proj.weight, None, K.GEMV_NONE))
 
 
 NemotronHFlashAttention2 = NemotronHAttention

@@ -79,6 +79,18 @@ class Qwen2KVCache:
             self.value_cache[layer_idx] = torch.cat([self.value_cache[layer_idx], v], dim=1)
         return self.key_cache[layer_idx], self.value_cache[layer_idx]
 
+    def clone(self) -> "Qwen2KVCache":
+        """Deep copy (with what `generate` left on the cache: pending ids, the prefill's drop bookkeeping): one prefilled
+        prompt forks into several questions."""
+        new = Qwen2KVCache(len(self.key_cache))
+        new.key_cache = [None if t is None else t.clone() for t in self.key_cache]
+        new.value_cache = [None if t is None else t.clone() for t in self.value_cache]
+        pending = getattr(self, "pending_ids", None)
+        new.pending_ids = None if pending is None else pending.clone()
+        if getattr(self, "pdrop_args", None) is not None:
+            new.pdrop_args = dict(self.pdrop_args)
+        return new
+
 
 class Qwen2RMSNorm(nn.Module):
     """:248-265."""

@@ -193,10 +193,13 @@ def fp8_quantise_ref(x, qmax: float = 440.0):
     x (B, L, H, D) -> fp32 tensor of the values the kernel multiplies.  The reference has no fp8
     path (its attention is bf16, modeling_qwen2.py:196-244): this restates the QUANTISER of the
     opt-in variant so that its MFMA / softmax arithmetic can be checked separately from the
-    quantisation error."""
+    quantisation error.
+    The scale is the fp32 quotient qmax / amax, correctly rounded, as in the kernel (`float / tensor` is
+    reciprocal-times-float in torch: one ulp off for amax = 33 x 2^k, which turns every v = 3 m x 2^j of such
+    a head into a different e4m3 neighbour; tests/test_attn_fp8_accuracy_gpu.py has such heads)."""
     xf = x.float()
     amax = xf.abs().amax(dim=(1, 3), keepdim=True)
-    qs = torch.where(amax > 0, qmax / amax, torch.ones_like(amax))
+    qs = torch.where(amax > 0, torch.full_like(amax, qmax) / amax, torch.ones_like(amax))
     q8 = (xf * qs).to(torch.float8_e4m3fn).float()
     return q8 / qs
 

@@ -6,12 +6,15 @@ The reference's attention arithmetic is bf16, so this opt-in variant is judged b
       relative per element, averaged over the keys of a row), the fp32 accumulation order and the
       bf16 output rounding;
   (b) against the bf16 kernel on the original inputs: adds the e4m3 rounding of q, k, v.
-Both bounds are written below as relative L2 error of the whole output and as a per-element bound."""
+Both bounds are written below as relative L2 error of the whole output and as a per-element bound.  Beside (a) stands the
+row bound of tests/attn_fp8_accuracy.py: the two above accept a last key or a tail tile missing from P.V
+(tests/test_attn_fp8_accuracy_cpu.py)."""
 import math
 
 import pytest
 import torch
 
+from attn_fp8_accuracy import FP8_ROW_BOUND, SWITCH_SHAPE, assert_rows_close, random_case, spiked_case
 from oracle import ops as R
 
 pytestmark = pytest.mark.gpu
@@ -73,6 +76,7 @@ def test_fp8_attention_vs_oracle_on_quantised_inputs_and_vs_bf16(K, B, Lq, Lk, H
     qd, kd, vd = R.fp8_quantise_ref(q), R.fp8_quantise_ref(k), R.fp8_quantise_ref(v)
     o_ref, lse_ref = R.attention_ref(qd, kd, vd, causal)
     check(o8, o_ref, TOL_VS_QUANTISED_ORACLE, "fp8 vs oracle on quantised inputs")
+    assert_rows_close(o8, o_ref, torch.bfloat16, f"fp8 {(B, Lq, Lk, Hq, Hkv, D, causal)}", bound=FP8_ROW_BOUND)
     # the row sum is taken over the unrounded P, so the log-sum-exp sees only the matrix pipe's fp8
     # accumulation of q~ . k~ (not a plain fp32 fmaf chain: ~1e-3 relative on a logit)
     assert (lse8.cpu() - lse_ref).abs().max() < 2e-2, "lse"
@@ -98,15 +102,15 @@ def test_fp8_attention_spiked_max_and_scale_spread(K):
     o8 = K.flash_attn_fp8_func(q.to(DEV), k.to(DEV), v.to(DEV), causal=True)
     for h in range(H):
         check(o8[:, :, h], o_ref[:, :, h], TOL_VS_QUANTISED_ORACLE, f"head {h}", vmax=float(v[:, :, h].float().abs().max()))
+    assert all(torch.equal(a, b) for a, b in zip((q, k, v), spiked_case()[:3])), "the CPU test judges these inputs"
+    assert_rows_close(o8, o_ref, torch.bfloat16, "fp8 spiked maximum, scale spread", bound=FP8_ROW_BOUND)
 
 
 def test_fp8_switch_routes_flash_attn_func(K):
     """`kernels.fp8_attention()` sends flash_attn_func (and the model code built on it) to the fp8
     kernel; short key sequences (decode) and the default state stay on bf16."""
-    g = torch.Generator(device=DEV).manual_seed(3)
-    q = torch.randn(1, 512, 4, 128, device=DEV, generator=g).bfloat16()
-    k = torch.randn(1, 512, 2, 128, device=DEV, generator=g).bfloat16()
-    v = torch.randn(1, 512, 2, 128, device=DEV, generator=g).bfloat16()
+    q, k, v, o_ref, _ = random_case(*SWITCH_SHAPE, torch.bfloat16)       # inputs the CPU test judges the row bound on
+    q, k, v = q.to(DEV), k.to(DEV), v.to(DEV)
     o16 = K.flash_attn_func(q, k, v, causal=True)
     with K.fp8_attention(min_keys=256):
         o8 = K.flash_attn_func(q, k, v, causal=True)
@@ -116,3 +120,4 @@ def test_fp8_switch_routes_flash_attn_func(K):
     assert torch.equal(short, K.flash_attn_func(q[:, :1], k[:, :100], v[:, :100], causal=True))
     assert torch.equal(decode, K.flash_attn_func(q[:, -1:], k, v, causal=True)), "decode step must stay on the bf16 kernel, bit for bit"
     assert not torch.equal(o8, o16) and torch.equal(K.flash_attn_func(q, k, v, causal=True), o16)
+    assert_rows_close(o8, o_ref, torch.bfloat16, "fp8 through the flash_attn_func switch", bound=FP8_ROW_BOUND)

@@ -544,6 +544,29 @@ int tv_gather_rows(const void* src, const int64_t* index, void* dst,
                    int64_t dst_stride, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Sampled decoding: ONE token per row of fp32 logits by temperature / top-k / top-p sampling, in one launch, in the
+ * place of the decode step's argmax (the reference's second front-end exposes temperature / top_p / top_k:
+ * eval/vllm_inference/vllm_infer.py).  logits (batch, vocab) fp32 with row_stride in elements (rows need not be 16-byte
+ * aligned); out_ids (batch) int64; draws (batch) int64 and streams (batch) int32 in DEVICE memory: the draw index and
+ * the stream of every row, read by the kernel, so that a captured step replays with new draw indices; diag NULL or
+ * (batch, 4) int32 = {tokens kept, float bits of the smallest kept s, the random word, 0}.
+ *   s_i = z_i * inv_temperature (one fp32 multiply; inv_temperature = fp32(1 / T), T > 0), m = max s,
+ *   q_i = floor(exp(s_i - m) * 2^40): every mass is an integer sum of q (order-independent; vocab <= 2^18);
+ *   top_k (0 or >= vocab: off): keep s_i >= the k-th largest s — ties at the threshold are all kept; W = their mass;
+ *   top_p (>= 1: off; applied after top_k): keep i iff the mass of the kept tokens with s > s_i is < top_p * W;
+ *   u = Philox4x32-10(counter (draw lo, draw hi, stream, 0), key (seed lo, seed hi))[0], r = (W_kept * u) >> 32;
+ *   out = the smallest kept index whose inclusive prefix sum of q over the kept set, in index order, exceeds r.
+ * A pure function of (row, parameters, seed, draw, stream): bitwise reproducible, a row's result does not depend on
+ * the other rows or on batch.  Rows that hold NaN or whose maximum is infinite are outside the contract; the id
+ * written is still in [0, vocab).  Null pointers, batch / vocab < 1, inv_temperature <= 0, top_p <= 0, top_k < 0:
+ * TV_ERR_BAD_ARG; vocab > 2^18: TV_ERR_UNSUPPORTED.  No workspace, no atomics on global memory, no host
+ * synchronisation.  Purely additive: tv_abi_version() stays 13.
+ * --------------------------------------------------------------------- */
+int tv_sample_logits_fwd(const void* logits, void* out_ids, const void* draws, const void* streams, void* diag,
+                         int batch, int vocab, int64_t row_stride, int64_t seed, float inv_temperature, int top_k,
+                         float top_p, void* stream);
+
+/* ------------------------------------------------------------------------
  * Qwen2 backbone ("next" row, BASELINE config 5).
  * tv_rope_fwd: rotary embedding in place on x (rows, heads, headdim) with element
  *   strides (x_stride_l, x_stride_h); cos / sin (rows, headdim) contiguous in x's

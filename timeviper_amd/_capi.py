@@ -69,6 +69,7 @@ SIGNATURES = {
     "tv_attn_rank_scores": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _i, _i, _f, _i, _p, _z, _p]),
     "tv_attn_rank_logits": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _f, _i, _p]),
     "tv_attn_rank_scores_from_logits": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "tv_sample_logits_fwd": (_i, [_p] * 5 + [_i, _i, _l, _l, _f, _i, _f, _p]),
     "tv_gather_rows": (_i, [_p, _p, _p, _l, _i, _l, _l, _i, _p]),
     "tv_uniform_keep_indices": (_i, [_p, _l, _l, _l, _p]),
     "tv_dropped_indices": (_i, [_p, _l, _l, _l, _p, _p]),

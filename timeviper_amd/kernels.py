@@ -925,6 +925,37 @@ def gather_rows(src: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def sample_logits(logits, draws, streams, seed, temperature=1.0, top_k=0, top_p=1.0, out=None, diag=None):
+    """One token id per row of fp32 `logits` (B, V) by temperature / top-k / top-p sampling: one launch, in the place of
+    the decode step's `argmax` (tv_sample_logits_fwd; the contract is in include/timeviper_hip.h and DESIGN.md).
+    `draws` (B,) int64 and `streams` (B,) int32 live on the GPU: row b is drawn with Philox4x32-10 at counter
+    (draws[b], streams[b]) under the key `seed`, so a captured step replays with the draw indices then in memory.
+    1 / temperature is formed in double and rounded once to fp32; `top_k` 0 (or >= V) and `top_p` >= 1 are off.
+    `out` (B,) int64 and `diag` (B, 4) int32 {kept, float bits of the smallest kept logit / T, random word, 0} are
+    written in place when given.  Rows may be strided (`logits3d[:, -1]`); no copy is made."""
+    _gpu(logits, draws, streams, out, diag)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise TimeViperHipError("sample_logits: logits must be (B, V) fp32 with contiguous rows")
+    B, V = logits.shape
+    if draws.dtype != torch.int64 or streams.dtype != torch.int32 or draws.numel() != B or streams.numel() != B \
+            or not draws.is_contiguous() or not streams.is_contiguous():
+        raise TimeViperHipError("sample_logits: draws (B,) int64 and streams (B,) int32, contiguous")
+    if not float(temperature) > 0.0:
+        raise TimeViperHipError("sample_logits: the temperature must be positive (0 is greedy decoding: argmax)")
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    elif out.dtype != torch.int64 or out.numel() != B or not out.is_contiguous():
+        raise TimeViperHipError("sample_logits: out must be (B,) int64, contiguous")
+    if diag is not None and (diag.dtype != torch.int32 or diag.numel() != 4 * B or not diag.is_contiguous()):
+        raise TimeViperHipError("sample_logits: diag must be (B, 4) int32, contiguous")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    check(_capi.lib().tv_sample_logits_fwd(_p(logits), _p(out), _p(draws), _p(streams), _p(diag), B, V,
+                                           logits.stride(0), seed - (1 << 64) if seed >> 63 else seed,
+                                           1.0 / float(temperature), int(top_k), min(float(top_p), 1.0), _stream()),
+          "tv_sample_logits_fwd")
+    return out
+
+
 def uniform_keep_indices(n_tokens: int, keep: int, offset: int = 0, device="cuda"):
     """torch.linspace(0, n-1, keep, dtype=long) with CPU semantics, + offset
     (modeling_nano.py:1946-1957), produced on the GPU, bit-exact."""

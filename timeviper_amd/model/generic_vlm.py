@@ -290,15 +290,23 @@ class GenericTimeViperVLM(nn.Module):
         Conversations: `return_past_key_values=True` returns `(result, cache)`; the cache records in `pending_ids` the
         ids emitted but not yet run through the model.  `past_key_values=cache` with the next turn's `input_ids` (text
         only) feeds pending ids + new ids + `answer_prompt` through ONE continuation forward of that cache instead of
-        a new prefill, then decodes as usual."""
+        a new prefill, then decodes as usual.
+        Sampled decoding: `do_sample=True` with `temperature` (> 0; default 1), `top_k` (0: off), `top_p` (>= 1: off) —
+        the arguments of the reference's second front-end (eval/vllm_inference/vllm_infer.py) — and `seed` (required:
+        there is no hidden global random state) draws every token with ONE launch of `kernels.sample_logits` in the place
+        of the argmax, inside the captured step where there is one.  The first new token is draw 0 of the stream
+        `sample_stream` (default 0), the n-th draw n - 1: the same call returns the same ids, graphed or not.
+        `do_sample=False` (any temperature) and `do_sample=True, temperature=0` decode greedily.  `speculative=D` with
+        sampling decodes plainly; `repetition_penalty != 1` and `num_beams > 1` raise NotImplementedError."""
         input_ids = args[0] if args else kwargs.pop("input_ids", None)
         pixel_values = kwargs.pop("pixel_values", None)
         pixel_values_videos = kwargs.pop("pixel_values_videos", None)
         attention_mask = kwargs.pop("attention_mask", None)
         max_new_tokens = int(kwargs.pop("max_new_tokens", 128))
         return_ids = bool(kwargs.pop("return_ids", False)) or bool(kwargs.pop("return_dict_in_generate", False))
-        if kwargs.pop("do_sample", False):
-            raise NotImplementedError("only greedy decoding is on the evaluation path")
+        from .llm.sampling import Sampler, sampling_arguments
+        sampling = sampling_arguments(kwargs, "generate")      # None: greedy
+        sample_stream = int(kwargs.pop("sample_stream", 0))
         eos = kwargs.pop("eos_token_id", None)
         eos = self.eos_token_ids_to_use if eos is None else eos
         eos = set(int(t) for t in (eos if isinstance(eos, (list, tuple)) else [eos]))
@@ -343,15 +351,18 @@ class GenericTimeViperVLM(nn.Module):
                                     cache_position=torch.tensor([past_len]), position_ids=pos, train_pdrop_args=pdargs)
         new_tokens: List[int] = []
         fed = 0                               # how many of them went through the model
-        tok = out.logits[:, -1].argmax(-1)
+        # sampled decoding: the first token is draw 0 of the stream, the n-th new token draw n - 1 (llm/sampling.py)
+        sampler = None if sampling is None else Sampler(self.device, streams=(sample_stream,), **sampling)
+        pick = (lambda logits: logits.argmax(-1)) if sampler is None else sampler.sample
+        tok = pick(out.logits[:, -1])
         self.last_generate_stats = {"speculative": False, "steps": 0, "drafted": 0, "accepted": 0, "emitted": 0,
                                     "graphed": False, "replays": 0, "graphs": 0, "capture_error": None}
-        n_drafts = self._speculative_drafts(speculative, cache, max_new_tokens)
+        n_drafts = self._speculative_drafts(speculative, cache, max_new_tokens, sampled=sampler is not None)
         if n_drafts:
             history = [int(t) for t in prompt_ids.reshape(-1).tolist()]
             new_tokens, fed = self._speculative_decode(cache, int(tok), n_drafts, draft_fn, history, max_new_tokens, eos, pdargs)
             return self._finish_generate(new_tokens, fed, cache, return_ids, return_cache)
-        stepper = self._graphed_decode_step(cache, max_new_tokens, pdargs)
+        stepper = self._graphed_decode_step(cache, max_new_tokens, pdargs, sampler)
         for _ in range(max_new_tokens):
             t = int(tok)
             new_tokens.append(t)
@@ -366,7 +377,7 @@ class GenericTimeViperVLM(nn.Module):
             out = self.llm_backbone(input_ids=mi["input_ids"], past_key_values=cache, use_cache=True,
                                     cache_position=mi["cache_position"], position_ids=mi["position_ids"],
                                     train_pdrop_args=pdargs)
-            tok = out.logits[:, -1].argmax(-1)
+            tok = pick(out.logits[:, -1])
         self.last_generate_stats.update(steps=fed, emitted=len(new_tokens), graphed=stepper is not None
                                         and stepper.graph is not None)
         return self._finish_generate(new_tokens, fed, cache, return_ids, return_cache)
@@ -379,12 +390,13 @@ class GenericTimeViperVLM(nn.Module):
             else tokenizer.decode(ids[0], skip_special_tokens=False).strip()
         return (result, cache) if return_cache else result
 
-    def _speculative_drafts(self, speculative, cache, max_new_tokens) -> int:
+    def _speculative_drafts(self, speculative, cache, max_new_tokens, sampled: bool = False) -> int:
         """Drafts per step D for `generate(speculative=...)`, or 0 where the stack is out of the feature's scope and the
         tokens are decoded plainly: anything but the Nemotron-H hybrid with its hybrid cache (Qwen2's rotary positions),
         fp8 attention, on the GPU anything but bf16 with attention head_dim 128 and (D + 1) x Hq / Hkv <= 128 columns
         (tv_attn_append_fwd with a device-side key count), TV_DECODE_GRAPH=0 there (an eager step of ~400 launches loses
-        more than the drafts win)."""
+        more than the drafts win), sampled decoding (verifying drafts under a sampler is rejection sampling: not
+        implemented; the tokens are sampled plainly)."""
         if speculative is None or speculative is False:
             return 0
         from .llm.nano import HybridMambaAttentionDynamicCache, NemotronHForCausalLM, continue_t_seq
@@ -394,7 +406,7 @@ class GenericTimeViperVLM(nn.Module):
         if D < 1:
             raise ValueError("generate(speculative=D): D >= 1 drafts per step")
         llm = self.llm_backbone.llm
-        if (not isinstance(llm, NemotronHForCausalLM) or not isinstance(cache, HybridMambaAttentionDynamicCache)
+        if (sampled or not isinstance(llm, NemotronHForCausalLM) or not isinstance(cache, HybridMambaAttentionDynamicCache)
                 or not cache.attention_layers or max_new_tokens < 2 or D + 1 > continue_t_seq() or K._ATTN_FP8["on"]
                 or llm.dtype not in (torch.bfloat16, torch.float32)):
             return 0
@@ -480,7 +492,7 @@ class GenericTimeViperVLM(nn.Module):
 
     @torch.inference_mode()
     def generate_branches(self, questions, past_key_values=None, max_new_tokens: int = 128, eos_token_id=None,
-                          answer_prompt: Optional[str] = None, return_ids: bool = False) -> list:
+                          answer_prompt: Optional[str] = None, return_ids: bool = False, **sampling_kwargs) -> list:
         """Several questions about ONE prefilled video: `questions` is a list of 1..16 id tensors (1, T_b), text only,
         `past_key_values` the cache a `generate(..., return_past_key_values=True)` (or a prefill forward) left.  Result b
         is what `generate(questions[b], past_key_values=cache.clone(), ...)` with the same arguments returns; the cache
@@ -494,7 +506,16 @@ class GenericTimeViperVLM(nn.Module):
         rides along as a padding row until the last one is done.  The step is one captured graph where plain `generate`
         would capture its step (`TV_DECODE_GRAPH`).  Out of scope (`_branch_scope`: Qwen2, fp32 on the GPU, more than
         16 questions, ...) the questions run one after the other on clones.  `last_generate_stats`: branched, branches,
-        steps (forwards), graphed."""
+        steps (forwards), graphed.
+
+        Sampled decoding (`do_sample=True, temperature, top_k, top_p, seed`, as in `generate`): branch b draws from
+        stream b, its n-th answer token is draw n - 1 — result b equals `generate(questions[b],
+        past_key_values=cache.clone(), do_sample=True, seed=seed, sample_stream=b, ...)`.  `[q] * n` is n samples of one
+        question for one prefill."""
+        from .llm.sampling import Sampler, sampling_arguments
+        sampling = sampling_arguments(sampling_kwargs, "generate_branches")
+        if sampling_kwargs:
+            raise TypeError(f"generate_branches: unexpected arguments {sorted(sampling_kwargs)}")
         cache = past_key_values
         if cache is None:
             raise ValueError("generate_branches: past_key_values (the prefilled cache the questions are about) is required")
@@ -504,9 +525,11 @@ class GenericTimeViperVLM(nn.Module):
             raise ValueError("generate_branches: at least one question, each of at least one id")
         if not self._branch_scope(cache, B):
             results, steps, graphed = [], 0, False
-            for q in questions:
+            for b, q in enumerate(questions):
+                sample = {} if sampling is None else dict(sampling, do_sample=True, sample_stream=b)
                 results.append(self.generate(q, past_key_values=cache.clone(), max_new_tokens=max_new_tokens,
-                                             eos_token_id=eos_token_id, answer_prompt=answer_prompt, return_ids=return_ids))
+                                             eos_token_id=eos_token_id, answer_prompt=answer_prompt, return_ids=return_ids,
+                                             **sample))
                 steps += self.last_generate_stats["steps"]
                 graphed = graphed or bool(self.last_generate_stats["graphed"])
             self.last_generate_stats = {"branched": False, "branches": B, "steps": steps, "graphed": graphed}
@@ -532,11 +555,14 @@ class GenericTimeViperVLM(nn.Module):
         def step_fn(ids):
             return self.llm_backbone(input_ids=ids, past_key_values=bs, use_cache=True, cache_position=host_pos,
                                      position_ids=dev_pos, train_pdrop_args=pdargs).logits
+        # branch b samples from stream b; its draw index (the tokens it has emitted) is written from the host every step
+        sampler = None if sampling is None else Sampler(self.device, streams=range(B), advance=False, **sampling)
+        pick = (lambda logits: logits.argmax(-1)) if sampler is None else sampler.sample
         stepper = None
         if (os.environ.get("TV_DECODE_GRAPH", "1") != "0" and self.device.type == "cuda" and max_new_tokens >= 8
                 and self.dtype == torch.bfloat16):
             from .llm.decode_graph import GraphedDecodeStep
-            stepper = GraphedDecodeStep(step_fn, bs, B, self.device)
+            stepper = GraphedDecodeStep(step_fn, bs, B, self.device, sampler=sampler)
         new_tokens: List[List[int]] = [[] for _ in range(B)]
         done = [max_new_tokens <= 0] * B
         steps = 0
@@ -544,10 +570,12 @@ class GenericTimeViperVLM(nn.Module):
             # branch b feeds its prompt, then its own last token; a finished branch rides along as a padding row
             row = [f[steps] if steps < len(f) else (t[-1] if t else 0) for f, t in zip(feeds, new_tokens)]
             ids = torch.tensor(row, dtype=torch.long, device=self.device).view(B, 1)
+            if sampler is not None:
+                sampler.set_draws([len(t) for t in new_tokens])
             if stepper is not None:
                 nxt = stepper.step(ids)
             else:
-                nxt = step_fn(ids)[:, -1].argmax(-1)
+                nxt = pick(step_fn(ids)[:, -1])
                 bs.advance_static_device()
             steps += 1
             nxt = nxt.reshape(-1).tolist()
@@ -566,7 +594,7 @@ class GenericTimeViperVLM(nn.Module):
                            else tokenizer.decode(ids[0], skip_special_tokens=False).strip())
         return results
 
-    def _graphed_decode_step(self, cache, max_new_tokens, pdargs):
+    def _graphed_decode_step(self, cache, max_new_tokens, pdargs, sampler=None):
         """The decode step behind `generate` as a captured graph (llm/decode_graph.py) where the stack allows it: the
         Nemotron-H hybrid (no positional encoding), bf16, attention head_dim 128 (tv_attn_decode_fwd), on the GPU, and
         enough tokens to pay for two eager warm-up steps and the capture.  TV_DECODE_GRAPH=0 keeps the eager loop."""
@@ -585,7 +613,7 @@ class GenericTimeViperVLM(nn.Module):
         def step_fn(ids):
             return self.llm_backbone(input_ids=ids, past_key_values=cache, use_cache=True, cache_position=host_pos,
                                      position_ids=dev_pos, train_pdrop_args=pdargs).logits
-        return GraphedDecodeStep(step_fn, cache, 1, self.device)
+        return GraphedDecodeStep(step_fn, cache, 1, self.device, sampler=sampler)
 
     @classmethod
     def from_pretrained(cls, pretrained_checkpoint, model_id: str, vision_backbone: VisionBackbone,

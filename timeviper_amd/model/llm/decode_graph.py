@@ -26,7 +26,9 @@ __all__ = ["GraphedDecodeStep", "GraphedSpecStep"]
 
 
 class GraphedDecodeStep:
-    """`step(token_ids)` -> next token ids (greedy), the same arithmetic as the eager loop.
+    """`step(token_ids)` -> next token ids — greedy, or drawn by `sampler` (llm/sampling.py: one launch of
+    `kernels.sample_logits` in the place of the argmax, its draw indices in device memory) —, the same arithmetic as the
+    eager loop.
 
     step_fn(ids) runs the language model on ONE token per sequence — ids is a (B, 1) int64 tensor that lives at a fixed
     address — against `cache` (already in static-decode mode) and returns the logits of that token, (B, V) or
@@ -35,10 +37,10 @@ class GraphedDecodeStep:
     cache's host bookkeeping and keeps running the eager step (`capture_error` holds the reason)."""
 
     def __init__(self, step_fn: Callable[[torch.Tensor], torch.Tensor], cache, batch_size: int, device,
-                 warmup: int = 2):
+                 warmup: int = 2, sampler=None):
         if not getattr(cache, "static_decode", False):
             raise RuntimeError("GraphedDecodeStep: call cache.begin_static_decode(max_new_tokens) first")
-        self.step_fn, self.cache, self.warmup = step_fn, cache, int(warmup)
+        self.step_fn, self.cache, self.warmup, self.sampler = step_fn, cache, int(warmup), sampler
         self.ids = torch.zeros((batch_size, 1), dtype=torch.int64, device=device)
         self.next_ids = None
         self.logits = None
@@ -49,7 +51,7 @@ class GraphedDecodeStep:
     def _run(self):
         logits = self.step_fn(self.ids)
         logits = logits[:, -1] if logits.dim() == 3 else logits
-        nxt = logits.argmax(-1)
+        nxt = logits.argmax(-1) if self.sampler is None else self.sampler.sample(logits)
         self.cache.advance_static_device()
         return logits, nxt
 

@@ -795,6 +795,61 @@ def test_graphed_decode_step_matches_the_eager_loop(pattern):
                            cache.kv_buffers(cache.attention_layers[0])[0][:, :310])
 
 
+def raise_once_under_capture(fn):
+    """`fn` as a step function whose first call under a stream capture fails: it runs the model — the host bookkeeping of
+    the step has advanced, the launches were recorded, none executed — and then raises an ordinary Python exception inside
+    the capture context.  No HIP call fails."""
+    raised = []
+
+    def step_fn(ids):
+        out = fn(ids)
+        if not raised and torch.cuda.is_current_stream_capturing():
+            raised.append(True)
+            raise RuntimeError("step function failed under capture (on purpose)")
+        return out
+    return step_fn, raised
+
+
+def test_graphed_decode_step_falls_back_to_the_eager_step_when_the_capture_fails():
+    """The capture of GraphedDecodeStep raises behind the model's forward: the step warns, puts the cache's host
+    bookkeeping back (the capture advanced every attention layer's length and ran no kernel) and runs eagerly, as does
+    every later one.  Teacher-forced against the eager loop, 8 tokens behind a 300-token prefill: the cache length after
+    every step, and the logits of every step at the bound of test_graphed_decode_step_matches_the_eager_loop."""
+    from timeviper_amd.model.llm.decode_graph import GraphedDecodeStep
+    from timeviper_amd.model.llm.nano import HybridMambaAttentionDynamicCache
+    cfg, model = _toy_hybrid_d128("M-*M*-")
+    g = torch.Generator(device=DEV).manual_seed(3)
+    prompt = torch.randint(0, 256, (1, 300), device=DEV, generator=g)
+    forced = torch.randint(0, 256, (8,), device=DEV, generator=g)
+    host_pos = torch.ones(1, dtype=torch.long)
+    with torch.inference_mode():
+        eager_cache = HybridMambaAttentionDynamicCache(cfg, 1, dtype=torch.bfloat16, device=DEV)
+        model(input_ids=prompt, past_key_values=eager_cache, use_cache=True, cache_position=torch.zeros(1, dtype=torch.long))
+        eager = [model(input_ids=t.view(1, 1), past_key_values=eager_cache, use_cache=True,
+                       cache_position=host_pos).logits[:, -1].clone() for t in forced]
+        cache = HybridMambaAttentionDynamicCache(cfg, 1, dtype=torch.bfloat16, device=DEV)
+        model(input_ids=prompt, past_key_values=cache, use_cache=True, cache_position=torch.zeros(1, dtype=torch.long))
+        cache.begin_static_decode(len(forced))
+        room = cache.static_room()
+        step_fn, raised = raise_once_under_capture(
+            lambda ids: model(input_ids=ids, past_key_values=cache, use_cache=True, cache_position=host_pos).logits)
+        stepper = GraphedDecodeStep(step_fn, cache, 1, DEV)
+        for i, t in enumerate(forced):
+            if i == stepper.warmup:              # the step that captures
+                with pytest.warns(RuntimeWarning, match="graph capture failed"):
+                    nxt = stepper.step(t.view(1, 1))
+                assert raised and isinstance(stepper.capture_error, RuntimeError)
+            else:
+                nxt = stepper.step(t.view(1, 1))
+            err = relerr(stepper.logits, eager[i])
+            print(f"step {i}: relerr {err:.3e}, cache length {cache.get_seq_length()}")
+            assert cache.get_seq_length() == 300 + i + 1, i
+            assert err < 3e-2, (i, err)
+            assert int(nxt) == int(stepper.logits.argmax(-1))
+        assert stepper.capture_error is not None and stepper.graph is None and stepper.calls == len(forced)
+        assert [cache._kv_len[i] for i in cache.attention_layers] == [308, 308] and cache.static_room() == room - 8
+
+
 def test_fused_decode_step_matches_the_unfused_one(monkeypatch):
     """TV_DECODE_FUSED (default): the decode token's norms / activations run in the prologues of tv_gemv_bf16_fwd; =0:
     stand-alone kernels + torch.nn.Linear.  Same rounding points, so the logits agree to the products' accumulation

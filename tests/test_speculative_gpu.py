@@ -243,6 +243,72 @@ def test_speculative_run_leaves_the_cache_of_single_steps(toy_prefilled, j):
             assert relerr(cache.key_cache[i], steps.key_cache[i]) < 2e-2, i
 
 
+NEAR_TIE = 3 * math.sqrt(2) * 3e-2      # top-2 gap / rms(logits) under which an argmax is not required to agree (_assert_no_near_tie)
+
+
+def test_graphed_spec_step_falls_back_to_the_eager_step_when_the_capture_fails(toy_prefilled):
+    """The first capture of GraphedSpecStep raises behind the model's forward (tests/test_model_gpu.py:
+    raise_once_under_capture): the step warns, puts the cache's host bookkeeping back and runs eagerly, as does every later
+    one.  Against a stepper that never captures, on a twin cache, fed the same t0 and the same D = 3 drafts (random ids from
+    a seeded generator: a step keeps t0 alone, so the two caches hold the same tokens whatever a near-tie does) for 8
+    steps: the same (k, p) as integers wherever the eager run's argmax has no near-tie — the toy model's greedy run has
+    some at every seed of the drafts (its second token: gap 0.11 rms) —, and after `end_speculation` the same lengths."""
+    from test_model_gpu import raise_once_under_capture
+    from timeviper_amd.model.llm.decode_graph import GraphedSpecStep
+    cfg, model, prefilled, truth = toy_prefilled
+    D, n_steps, n = 3, 8, 300
+    T = D + 1
+    one = torch.ones(1, dtype=torch.long)
+    gen = torch.Generator().manual_seed(0)
+    drafts = [torch.randint(0, cfg.vocab_size, (D,), generator=gen).tolist() for _ in range(n_steps)]
+
+    def forward(cache):
+        return lambda ids: model(input_ids=ids, past_key_values=cache, use_cache=True, cache_position=one,
+                                 logits_to_keep=ids.shape[1]).logits
+    with torch.inference_mode():
+        twin, seen = prefilled.clone(), []
+        twin.begin_speculation(T, n_steps * T)
+        run = forward(twin)
+
+        def watched(ids):
+            seen.append(run(ids).reshape(T, -1).float())
+            return seen[-1]
+        eager = GraphedSpecStep(watched, twin, T, DEV, graphed=False)
+        t0s, want = [truth[0]], []
+        for d in drafts:
+            want.append(eager.step(t0s[-1], d))
+            t0s.append(want[-1][1][want[-1][0] - 1])
+        twin.end_speculation()
+        lg = torch.cat(seen)
+        top2 = lg.topk(2, dim=-1).values
+        sure = ((top2[:, 0] - top2[:, 1]) / lg.pow(2).mean(-1).sqrt() > NEAR_TIE).view(n_steps, T).tolist()
+        ks = [k for k, _ in want]
+        print("tokens kept per step:", ks, "positions without a near-tie:", [sum(r) for r in sure])
+        assert sum(sum(r) for r in sure) >= n_steps * T // 2          # (23 of 32 on the CPU stand-ins)
+
+        cache = prefilled.clone()
+        cache.begin_speculation(T, n_steps * T)
+        step_fn, raised = raise_once_under_capture(forward(cache))
+        stepper = GraphedSpecStep(step_fn, cache, T, DEV, graphed=True)
+        for s, d in enumerate(drafts):
+            if s == stepper.warmup:              # the step that captures
+                with pytest.warns(RuntimeWarning, match="graph capture failed"):
+                    k, p = stepper.step(t0s[s], d)
+                assert raised and isinstance(stepper.capture_error, RuntimeError)
+            else:
+                k, p = stepper.step(t0s[s], d)
+            print(f"step {s}: k {k} / {want[s][0]}, p {p} / {want[s][1]}")
+            assert all(a == b for a, b, ok in zip(p, want[s][1], sure[s]) if ok), (s, p, want[s][1], sure[s])
+            assert k == want[s][0] or not all(sure[s][:want[s][0]]), (s, k, want[s][0])
+            if k != want[s][0]:                  # (a near-tie among the deciding positions: keep what the twin kept)
+                cache.commit(want[s][0])
+        assert stepper.capture_error is not None and not stepper.graphs and stepper.replays == 0
+        assert stepper.calls == n_steps
+        cache.end_speculation()
+    assert cache.get_seq_length() == twin.get_seq_length() == n + sum(ks)
+    assert cache._kv_len == twin._kv_len
+
+
 # ------------------------------------------------------------------ generate
 # Model / pixel seeds of the generate tests: per prompt the smallest seed (0, 1, 2, ...) for which the PLAIN run's top-2
 # logit gap exceeds 3 sqrt(2) 3e-2 rms(logits) at every one of the 16 generated positions (see _assert_no_near_tie; the

@@ -295,7 +295,7 @@ def bench_rows(st, roles_only=False, repeats=3):
                         assert k == keep, (k, keep)
                     torch.cuda.synchronize()
                     assert len(stp.graphs) == 2 and stp.capture_error is None, stp.capture_error
-                    first = cache._spec["flip"]
+                    first = cache.spec_parity()
                     ms = [replay_ms([stp.graphs[first], stp.graphs[first ^ 1]], st) for _ in range(repeats)]
                     t[keep], spread[keep] = statistics.median(ms), max(ms) - min(ms)
                     del stp, cache
@@ -371,7 +371,7 @@ def bench_end_to_end(st):
                     assert k == keep, (k, keep)
                 torch.cuda.synchronize()
                 assert len(stp.graphs) == 2 and stp.capture_error is None, stp.capture_error
-                first = cache._spec["flip"]          # the parity the next step runs on
+                first = cache.spec_parity()          # the parity the next step runs on
                 t[keep] = replay_ms([stp.graphs[first], stp.graphs[first ^ 1]], st)
                 del stp, cache
                 gc.collect()

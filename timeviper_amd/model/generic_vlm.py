@@ -307,9 +307,7 @@ class GenericTimeViperVLM(nn.Module):
         from .llm.sampling import Sampler, sampling_arguments
         sampling = sampling_arguments(kwargs, "generate")      # None: greedy
         sample_stream = int(kwargs.pop("sample_stream", 0))
-        eos = kwargs.pop("eos_token_id", None)
-        eos = self.eos_token_ids_to_use if eos is None else eos
-        eos = set(int(t) for t in (eos if isinstance(eos, (list, tuple)) else [eos]))
+        eos = self._eos_set(kwargs.pop("eos_token_id", None))
         llm = self.llm_backbone.llm
         cache = kwargs.pop("past_key_values", None)
         return_cache = bool(kwargs.pop("return_past_key_values", False))
@@ -382,13 +380,53 @@ class GenericTimeViperVLM(nn.Module):
                                         and stepper.graph is not None)
         return self._finish_generate(new_tokens, fed, cache, return_ids, return_cache)
 
+    def _eos_set(self, eos_token_id) -> set:
+        eos = self.eos_token_ids_to_use if eos_token_id is None else eos_token_id
+        return set(int(t) for t in (eos if isinstance(eos, (list, tuple)) else [eos]))
+
+    def _result(self, ids, return_ids):
+        """New ids (1, n) as `generate` returns them: decoded and stripped, or the tensor itself."""
+        tokenizer = self.llm_backbone.tokenizer
+        if return_ids or not hasattr(tokenizer, "decode"):
+            return ids
+        return tokenizer.decode(ids[0], skip_special_tokens=False).strip()
+
     def _finish_generate(self, new_tokens, fed, cache, return_ids, return_cache):
         ids = torch.tensor([new_tokens], device=self.device)
         cache.pending_ids = ids[:, fed:].clone()
-        tokenizer = self.llm_backbone.tokenizer
-        result = ids if return_ids or not hasattr(tokenizer, "decode") \
-            else tokenizer.decode(ids[0], skip_special_tokens=False).strip()
+        result = self._result(ids, return_ids)
         return (result, cache) if return_cache else result
+
+    def _step_fn(self, cache, batch_size, pdargs, logits_to_keep=None):
+        """step_fn(ids) of the steppers of llm/decode_graph.py: one forward behind the prefill over ids (batch_size, T)
+        against `cache` — the hybrid cache or a branch set — returning the logits of the last (`logits_to_keep`) positions."""
+        host_pos = torch.ones(1, dtype=torch.long)              # "not the prefill" for the mixers' host-side branch
+        dev_pos = torch.ones((batch_size, 1), dtype=torch.long, device=self.device)
+
+        def step_fn(ids):
+            return self.llm_backbone(input_ids=ids, past_key_values=cache, use_cache=True, cache_position=host_pos,
+                                     position_ids=dev_pos, train_pdrop_args=pdargs, logits_to_keep=logits_to_keep).logits
+        return step_fn
+
+    def _hybrid_step_scope(self, cache, columns=None) -> bool:
+        """What the captured decode step, the speculative step and the branched step ask alike: the Nemotron-H hybrid with
+        its hybrid cache, attention layers in it, on the GPU head_dim 128 (the split-KV kernels).  `columns`: the tokens or
+        branches that share one attention launch (tv_attn_append_fwd, tv_attn_branch_fwd) — then also no fp8 attention,
+        bf16 (on the CPU fp32 too) and on the GPU columns x Hq / Hkv <= 128; None: the one-token step, bound by none of it."""
+        from .llm.nano import HybridMambaAttentionDynamicCache, NemotronHForCausalLM
+        from .. import kernels as K
+        llm = self.llm_backbone.llm
+        if (not isinstance(llm, NemotronHForCausalLM) or not isinstance(cache, HybridMambaAttentionDynamicCache)
+                or not cache.attention_layers):
+            return False
+        on_gpu = self.device.type == "cuda"
+        if on_gpu and cache.key_cache[cache.attention_layers[0]].shape[-1] != 128:
+            return False
+        if columns is None:
+            return True
+        cfg = llm.config
+        return (not K._ATTN_FP8["on"] and llm.dtype in ((torch.bfloat16,) if on_gpu else (torch.bfloat16, torch.float32))
+                and not (on_gpu and columns * (cfg.num_attention_heads // cfg.num_key_value_heads) > 128))
 
     def _speculative_drafts(self, speculative, cache, max_new_tokens, sampled: bool = False) -> int:
         """Drafts per step D for `generate(speculative=...)`, or 0 where the stack is out of the feature's scope and the
@@ -399,23 +437,15 @@ class GenericTimeViperVLM(nn.Module):
         implemented; the tokens are sampled plainly)."""
         if speculative is None or speculative is False:
             return 0
-        from .llm.nano import HybridMambaAttentionDynamicCache, NemotronHForCausalLM, continue_t_seq
+        from .llm.nano import continue_t_seq
         from .llm.speculative import DEFAULT_DRAFTS
-        from .. import kernels as K
         D = DEFAULT_DRAFTS if speculative is True else int(speculative)
         if D < 1:
             raise ValueError("generate(speculative=D): D >= 1 drafts per step")
-        llm = self.llm_backbone.llm
-        if (sampled or not isinstance(llm, NemotronHForCausalLM) or not isinstance(cache, HybridMambaAttentionDynamicCache)
-                or not cache.attention_layers or max_new_tokens < 2 or D + 1 > continue_t_seq() or K._ATTN_FP8["on"]
-                or llm.dtype not in (torch.bfloat16, torch.float32)):
+        if sampled or max_new_tokens < 2 or D + 1 > continue_t_seq() or not self._hybrid_step_scope(cache, columns=D + 1):
             return 0
-        if self.device.type == "cuda":
-            cfg = llm.config
-            if (llm.dtype != torch.bfloat16 or cache.key_cache[cache.attention_layers[0]].shape[-1] != 128
-                    or (D + 1) * (cfg.num_attention_heads // cfg.num_key_value_heads) > 128
-                    or os.environ.get("TV_DECODE_GRAPH", "1") == "0"):
-                return 0
+        if self.device.type == "cuda" and os.environ.get("TV_DECODE_GRAPH", "1") == "0":
+            return 0
         return D
 
     def _speculative_decode(self, cache, first, D, draft_fn, history, max_new_tokens, eos, pdargs):
@@ -435,12 +465,7 @@ class GenericTimeViperVLM(nn.Module):
             stats["emitted"] = 1
             return new_tokens, fed
         cache.begin_speculation(T, max_new_tokens)
-        host_pos = torch.ones(1, dtype=torch.long)              # "not the prefill" for the mixers' host-side branch
-        dev_pos = torch.ones((1, 1), dtype=torch.long, device=self.device)
-
-        def step_fn(ids):
-            return self.llm_backbone(input_ids=ids, past_key_values=cache, use_cache=True, cache_position=host_pos,
-                                     position_ids=dev_pos, train_pdrop_args=pdargs, logits_to_keep=ids.shape[1]).logits
+        step_fn = self._step_fn(cache, 1, pdargs, logits_to_keep=T)
         stepper = GraphedSpecStep(step_fn, cache, T, self.device, graphed=self.device.type == "cuda")
         done = False
         while not done:
@@ -476,19 +501,7 @@ class GenericTimeViperVLM(nn.Module):
         hybrid cache, 1..16 branches, no fp8 attention; on the GPU bf16, attention head_dim 128 and
         branches x Hq / Hkv <= 128 columns (tv_attn_branch_fwd).  Anything else runs question by question on clones."""
         from .llm.branch import MAX_BRANCHES
-        from .llm.nano import HybridMambaAttentionDynamicCache, NemotronHForCausalLM
-        from .. import kernels as K
-        llm = self.llm_backbone.llm
-        if (not isinstance(llm, NemotronHForCausalLM) or not isinstance(cache, HybridMambaAttentionDynamicCache)
-                or not cache.attention_layers or not 1 <= n_branches <= MAX_BRANCHES or K._ATTN_FP8["on"]
-                or llm.dtype not in (torch.bfloat16, torch.float32)):
-            return False
-        if self.device.type == "cuda":
-            cfg = llm.config
-            if (llm.dtype != torch.bfloat16 or cache.key_cache[cache.attention_layers[0]].shape[-1] != 128
-                    or n_branches * (cfg.num_attention_heads // cfg.num_key_value_heads) > 128):
-                return False
-        return True
+        return 1 <= n_branches <= MAX_BRANCHES and self._hybrid_step_scope(cache, columns=n_branches)
 
     @torch.inference_mode()
     def generate_branches(self, questions, past_key_values=None, max_new_tokens: int = 128, eos_token_id=None,
@@ -534,8 +547,7 @@ class GenericTimeViperVLM(nn.Module):
                 graphed = graphed or bool(self.last_generate_stats["graphed"])
             self.last_generate_stats = {"branched": False, "branches": B, "steps": steps, "graphed": graphed}
             return results
-        eos = self.eos_token_ids_to_use if eos_token_id is None else eos_token_id
-        eos = set(int(t) for t in (eos if isinstance(eos, (list, tuple)) else [eos]))
+        eos = self._eos_set(eos_token_id)
         if getattr(cache, "get_seq_length", None) and cache.get_seq_length() == 0:
             raise ValueError("generate_branches: the cache holds no prefill")
         tail: List[int] = []
@@ -549,12 +561,7 @@ class GenericTimeViperVLM(nn.Module):
         bs = cache.branch(B, suffix_cap=n_steps)
         bs.begin_static_decode(n_steps)
         pdargs = getattr(bs, "pdrop_args", self.pdrop_args if self.use_pdrop else None)      # (as `generate` reads the cache's)
-        host_pos = torch.ones(1, dtype=torch.long)              # "not the prefill" for the mixers' host-side branch
-        dev_pos = torch.ones((B, 1), dtype=torch.long, device=self.device)
-
-        def step_fn(ids):
-            return self.llm_backbone(input_ids=ids, past_key_values=bs, use_cache=True, cache_position=host_pos,
-                                     position_ids=dev_pos, train_pdrop_args=pdargs).logits
+        step_fn = self._step_fn(bs, B, pdargs)
         # branch b samples from stream b; its draw index (the tokens it has emitted) is written from the host every step
         sampler = None if sampling is None else Sampler(self.device, streams=range(B), advance=False, **sampling)
         pick = (lambda logits: logits.argmax(-1)) if sampler is None else sampler.sample
@@ -586,34 +593,18 @@ class GenericTimeViperVLM(nn.Module):
                 done[b] = nxt[b] in eos or len(new_tokens[b]) >= max_new_tokens
         self.last_generate_stats = {"branched": True, "branches": B, "steps": steps,
                                     "graphed": stepper is not None and stepper.graph is not None}
-        tokenizer = self.llm_backbone.tokenizer
-        results = []
-        for t in new_tokens:
-            ids = torch.tensor([t], device=self.device)
-            results.append(ids if return_ids or not hasattr(tokenizer, "decode")
-                           else tokenizer.decode(ids[0], skip_special_tokens=False).strip())
-        return results
+        return [self._result(torch.tensor([t], device=self.device), return_ids) for t in new_tokens]
 
     def _graphed_decode_step(self, cache, max_new_tokens, pdargs, sampler=None):
         """The decode step behind `generate` as a captured graph (llm/decode_graph.py) where the stack allows it: the
         Nemotron-H hybrid (no positional encoding), bf16, attention head_dim 128 (tv_attn_decode_fwd), on the GPU, and
         enough tokens to pay for two eager warm-up steps and the capture.  TV_DECODE_GRAPH=0 keeps the eager loop."""
         from .llm.decode_graph import GraphedDecodeStep
-        from .llm.nano import HybridMambaAttentionDynamicCache, NemotronHForCausalLM
-        llm = self.llm_backbone.llm
         if (os.environ.get("TV_DECODE_GRAPH", "1") == "0" or self.device.type != "cuda" or max_new_tokens < 8
-                or not isinstance(llm, NemotronHForCausalLM) or not isinstance(cache, HybridMambaAttentionDynamicCache)
-                or self.dtype != torch.bfloat16 or not cache.attention_layers
-                or cache.key_cache[cache.attention_layers[0]].shape[-1] != 128):
+                or self.dtype != torch.bfloat16 or not self._hybrid_step_scope(cache)):
             return None
         cache.begin_static_decode(max_new_tokens)
-        host_pos = torch.ones(1, dtype=torch.long)              # "not the prefill" for the mixers' host-side branch
-        dev_pos = torch.ones((1, 1), dtype=torch.long, device=self.device)
-
-        def step_fn(ids):
-            return self.llm_backbone(input_ids=ids, past_key_values=cache, use_cache=True, cache_position=host_pos,
-                                     position_ids=dev_pos, train_pdrop_args=pdargs).logits
-        return GraphedDecodeStep(step_fn, cache, 1, self.device, sampler=sampler)
+        return GraphedDecodeStep(self._step_fn(cache, 1, pdargs), cache, 1, self.device, sampler=sampler)
 
     @classmethod
     def from_pretrained(cls, pretrained_checkpoint, model_id: str, vision_backbone: VisionBackbone,

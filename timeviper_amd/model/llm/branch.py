@@ -17,6 +17,8 @@ that are not part of the fork): every step checks that the parent still holds th
 The set is always launch-parameter-static — the write slot and the per-branch key count live on the device — and offers
 the static-decode interface of the hybrid cache, so that `GraphedDecodeStep` captures the branched step with
 `batch_size = n` as it captures the plain one.  Whoever runs a step eagerly calls `advance_static_device()` behind it.
+The suffix rows are kept as the hybrid cache keeps its rows, by the same code (`nano.KVRows`: `_set_len`, `static_room`,
+`kv_buffers`, `advance_static_host`, `host_state` / `restore_host_state`); the rest of the cache interface is duck-typed.
 """
 from __future__ import annotations
 
@@ -24,12 +26,14 @@ from typing import List, Optional
 
 import torch
 
+from .nano import KVRows
+
 __all__ = ["BranchSet", "MAX_BRANCHES"]
 
 MAX_BRANCHES = 16        # kernels.flash_attn_branch's range (tv_attn_branch_fwd)
 
 
-class BranchSet:
+class BranchSet(KVRows):
     is_branch_set = True
     speculating = False
 
@@ -40,7 +44,7 @@ class BranchSet:
         if getattr(parent, "speculating", False):
             raise RuntimeError("branch: the cache is in speculation mode (provisional tokens are not part of it yet); "
                                "call end_speculation() first")
-        if not parent.attention_layers or any(parent._kv_len[i] == 0 for i in parent.attention_layers):
+        if not parent.holds_prefill():
             raise RuntimeError("branch: the cache holds no prefill (every attention layer holding its tokens)")
         if parent.key_cache[parent.attention_layers[0]].shape[0] != 1:
             raise RuntimeError("branch: the parent holds one sequence")
@@ -57,7 +61,7 @@ class BranchSet:
         # the prefix: the parent's own tensors, (1, L_i, Hkv, D)
         self.prefix_len = {i: parent._kv_len[i] for i in self.attention_layers}
         self.prefix = {i: (parent.key_cache[i], parent.value_cache[i]) for i in self.attention_layers}
-        # the suffixes, under the names the hybrid cache (and GraphedDecodeStep's bookkeeping) uses for its rows
+        # the suffixes, under the names the hybrid cache uses for its rows (KVRows)
         self._kv_buf = [None] * nl
         self._kv_len = [0] * nl
         self.key_cache = [parent.key_cache[i][:0] for i in range(nl)]
@@ -80,7 +84,7 @@ class BranchSet:
             if have:
                 kb[:, :have], vb[:, :have] = self.key_cache[i], self.value_cache[i]
             self._kv_buf[i] = (kb, vb)
-            self.key_cache[i], self.value_cache[i] = kb[:, :have], vb[:, :have]
+            self._set_len(i, have)
 
     # ---- what the model's layers ask
     @property
@@ -113,8 +117,7 @@ class BranchSet:
                                "reserved too little)")
         kb.index_copy_(1, self._pos, key_states)
         vb.index_copy_(1, self._pos, value_states)
-        self._kv_len[layer_idx] = have + 1
-        self.key_cache[layer_idx], self.value_cache[layer_idx] = kb[:, :have + 1], vb[:, :have + 1]
+        self._set_len(layer_idx, have + 1)
         kp, vp = self.prefix[layer_idx]
         return kp, vp, kb, vb, self._lens
 
@@ -141,9 +144,6 @@ class BranchSet:
     def end_static_decode(self):
         self.static_decode = False
 
-    def static_room(self) -> int:
-        return min(self._kv_buf[i][0].shape[1] - self._kv_len[i] for i in self.attention_layers)
-
     def advance_static_device(self):
         """Device side of one finished step (part of a captured graph; behind every eager step too)."""
         self._pos += 1
@@ -152,15 +152,8 @@ class BranchSet:
     def decode_lens(self, layer_idx):
         return self._lens
 
-    def kv_buffers(self, layer_idx):
-        """The suffix buffers of a layer, (n, cap, Hkv, D)."""
-        return self._kv_buf[layer_idx]
-
     def advance_static_host(self):
-        """Host side of one REPLAYED step: the bookkeeping `write` does when it runs."""
+        """Host side of one REPLAYED step: the check and the bookkeeping `write` does when it runs."""
         for i in self.attention_layers:
             self.check_parent(i)
-            n = self._kv_len[i] + 1
-            kb, vb = self._kv_buf[i]
-            self._kv_len[i] = n
-            self.key_cache[i], self.value_cache[i] = kb[:, :n], vb[:, :n]
+        super().advance_static_host()

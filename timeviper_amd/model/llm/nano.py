@@ -148,7 +148,46 @@ class CausalLMOutputWithPast:
 
 
 # ------------------------------------------------------------------- cache
-class HybridMambaAttentionDynamicCache:
+class KVRows:
+    """The rows every attention layer holds, for the hybrid cache and for `BranchSet` (llm/branch.py): `_kv_buf[i]` are a
+    layer's (k, v) capacity buffers, `_kv_len[i]` the rows of them in use, `key_cache[i]` / `value_cache[i]` the views of
+    exactly those rows.  `_set_len` is the one place that moves the three together."""
+
+    def _set_len(self, layer_idx, n):
+        """Layer `layer_idx` now holds `n` rows of its buffers."""
+        kb, vb = self._kv_buf[layer_idx]
+        self._kv_len[layer_idx] = n
+        self.key_cache[layer_idx], self.value_cache[layer_idx] = kb[:, :n], vb[:, :n]
+
+    def kv_buffers(self, layer_idx):
+        """The capacity buffers of a layer (static decode: what the attention kernel is handed, with `decode_lens`)."""
+        return self._kv_buf[layer_idx]
+
+    def static_room(self) -> int:
+        """Tokens the fixed buffers still take (a replayed graph writes where its device-side position says: the caller
+        must stop before the buffers end — GraphedDecodeStep checks this before every launch)."""
+        return min(self._kv_buf[i][0].shape[1] - self._kv_len[i] for i in self.attention_layers)
+
+    def advance_static_host(self):
+        """Host side of one REPLAYED step: the bookkeeping the step's cache write does when it runs."""
+        for i in self.attention_layers:
+            self._set_len(i, self._kv_len[i] + 1)
+
+    # What the host side of a step changes and no kernel reads: the rows every layer holds and, in speculation mode, the host
+    # side of `_spec`.  A graph capture runs it without running the step, so a failed capture has to put it back
+    # (llm/decode_graph.py).
+    def host_state(self):
+        return {i: self._kv_len[i] for i in self.attention_layers}, dict(self._spec["host"]) if self.speculating else None
+
+    def restore_host_state(self, state):
+        rows, spec = state
+        for i, n in rows.items():
+            self._set_len(i, n)
+        if spec is not None:
+            self._spec["host"].update(spec)
+
+
+class HybridMambaAttentionDynamicCache(KVRows):
     """Per-layer conv / ssm / key / value lists (reference :205-360).  SSM states
     are kept in fp32 (what the scan kernel returns and the decode kernel updates).
 
@@ -201,7 +240,7 @@ class HybridMambaAttentionDynamicCache:
         kb, vb = k_old.new_empty(shape), v_old.new_empty(shape)
         kb[:, :have], vb[:, :have] = k_old, v_old
         self._kv_buf[layer_idx] = (kb, vb)
-        self.key_cache[layer_idx], self.value_cache[layer_idx] = kb[:, :have], vb[:, :have]
+        self._set_len(layer_idx, have)
 
     def update(self, key_states, value_states, layer_idx, cache_kwargs=None):
         """key/value (B, L, Hkv, D) — sequence-major, the layout the attention kernel reads."""
@@ -221,38 +260,37 @@ class HybridMambaAttentionDynamicCache:
             vb.index_copy_(1, pos, value_states)
         else:
             kb[:, have:have + new], vb[:, have:have + new] = key_states, value_states
-        self._kv_len[layer_idx] = have + new
-        self.key_cache[layer_idx], self.value_cache[layer_idx] = kb[:, :have + new], vb[:, :have + new]
+        self._set_len(layer_idx, have + new)
         return self.key_cache[layer_idx], self.value_cache[layer_idx]
 
-    def kv_buffers(self, layer_idx):
-        """The capacity buffers of a layer (static decode: what the attention kernel is handed, with `decode_lens`)."""
-        return self._kv_buf[layer_idx]
+    def holds_prefill(self) -> bool:
+        """Behind a prefill: every attention layer holding its tokens."""
+        return bool(self.attention_layers) and all(self._kv_len[i] > 0 for i in self.attention_layers)
+
+    def _fix_buffers(self, room: int, seen: int):
+        """Room for `room` more rows in buffers that stay where they are, and per distinct cache length (token drop leaves
+        the attention layers behind a stage with fewer tokens than the ones in front of it) an int64 (1,) write slot and
+        an int32 (B,) key count on the device, shared by the layers that hold it.  `seen`: the count's lead over the slot
+        — 1 where a step's query sees the row it writes (static decode), 0 where a forward adds its own T (speculation)."""
+        self.end_static_decode()
+        for i in self.attention_layers:
+            self._reserve(i, self._kv_len[i] + room)
+        k0 = self.key_cache[self.attention_layers[0]]
+        self._static = {n: (torch.full((1,), n, dtype=torch.int64, device=k0.device),
+                            torch.full((k0.shape[0],), n + seen, dtype=torch.int32, device=k0.device))
+                        for n in sorted({self._kv_len[i] for i in self.attention_layers})}
+        self._static_of = {i: self._static[self._kv_len[i]] for i in self.attention_layers}
 
     # ---- static decode (fixed launch parameters; see GraphedDecodeStep)
     def begin_static_decode(self, max_new_tokens: int):
-        """Token drop (pdrop) leaves the attention layers behind a stage with fewer tokens than the ones in front of it:
-        one (write position, key count) pair per distinct length, shared by the layers that hold it."""
-        if not self.attention_layers or any(self._kv_len[i] == 0 for i in self.attention_layers):
+        """One token per step for the next `max_new_tokens` steps, every launch with the same parameters (`_fix_buffers`)."""
+        if not self.holds_prefill():
             raise RuntimeError("static decode starts behind a prefill (every attention layer holding its tokens)")
-        self.end_static_decode()
-        for i in self.attention_layers:
-            self._reserve(i, self._kv_len[i] + int(max_new_tokens))
-        k0 = self.key_cache[self.attention_layers[0]]
-        self._static = {}
-        for n in sorted({self._kv_len[i] for i in self.attention_layers}):
-            self._static[n] = (torch.full((1,), n, dtype=torch.int64, device=k0.device),
-                               torch.full((k0.shape[0],), n + 1, dtype=torch.int32, device=k0.device))
-        self._static_of = {i: self._static[self._kv_len[i]] for i in self.attention_layers}
+        self._fix_buffers(int(max_new_tokens), seen=1)
         self.static_decode = True
 
     def end_static_decode(self):
         self._static, self._static_of, self.static_decode = {}, {}, False
-
-    def static_room(self) -> int:
-        """Tokens the fixed buffers still take (a replayed graph writes where its device-side position says: the caller
-        must stop before the buffers end — GraphedDecodeStep checks this before every launch)."""
-        return min(self._kv_buf[i][0].shape[1] - self._kv_len[i] for i in self.attention_layers)
 
     def advance_static_device(self):
         """Device side of one finished step (part of the captured graph)."""
@@ -262,14 +300,6 @@ class HybridMambaAttentionDynamicCache:
 
     def decode_lens(self, layer_idx):
         return self._static_of[layer_idx][1]
-
-    def advance_static_host(self):
-        """Host side of one REPLAYED step: the bookkeeping `update` does when it runs."""
-        for i in self.attention_layers:
-            n = self._kv_len[i] + 1
-            kb, vb = self._kv_buf[i]
-            self._kv_len[i] = n
-            self.key_cache[i], self.value_cache[i] = kb[:, :n], vb[:, :n]
 
     def get_seq_length(self, layer_idx: Optional[int] = 0) -> int:
         if not self.attention_layers:
@@ -323,20 +353,14 @@ class HybridMambaAttentionDynamicCache:
         launch parameters every time (GraphedSpecStep)."""
         if self.speculating:
             raise RuntimeError("begin_speculation: already speculating")
-        if not self.attention_layers or any(self._kv_len[i] == 0 for i in self.attention_layers):
+        if not self.holds_prefill():
             raise RuntimeError("speculation starts behind a prefill (every attention layer holding its tokens)")
         t_max, max_new_tokens = int(t_max), int(max_new_tokens)
         if t_max < 1 or max_new_tokens < 0:
             raise ValueError("begin_speculation: t_max >= 1, max_new_tokens >= 0")
-        self.end_static_decode()
-        for i in self.attention_layers:
-            self._reserve(i, self._kv_len[i] + max_new_tokens + t_max)
+        self._fix_buffers(max_new_tokens + t_max, seen=0)
         k0 = self.key_cache[self.attention_layers[0]]
         dev, B = k0.device, k0.shape[0]
-        self._static = {n: (torch.full((1,), n, dtype=torch.int64, device=dev),
-                            torch.full((B,), n, dtype=torch.int32, device=dev))
-                        for n in sorted({self._kv_len[i] for i in self.attention_layers})}
-        self._static_of = {i: self._static[self._kv_len[i]] for i in self.attention_layers}
         d_in, G, N, H = self._mamba_dims
         slots = {}
         for i, c in enumerate(self.hybrid_override_pattern):
@@ -344,13 +368,16 @@ class HybridMambaAttentionDynamicCache:
                 dt = self.conv_states[i].dtype
                 mk = lambda n: torch.zeros(B * t_max * n, dtype=dt, device=dev)
                 slots[i] = [{"x": mk(d_in), "B": mk(G * N), "C": mk(G * N), "tail": mk(d_in + 2 * G * N + H)} for _ in range(2)]
-        self._spec = {"t_max": t_max, "room": max_new_tokens + t_max, "slots": slots, "flip": 0, "t_prev": 0,
+        self._spec = {"t_max": t_max, "room": max_new_tokens + t_max, "slots": slots,
                       "n_commit": torch.zeros(1, dtype=torch.int32, device=dev),
                       "kidx": torch.arange(self.conv_kernel_size, device=dev), "tidx": torch.arange(t_max, device=dev),
                       "base": {i: self._kv_len[i] for i in self.attention_layers},
-                      # host side: tokens kept of the forwards before the last one / of the last one — upper bounds, and
-                      # flagged as such, while a device-side commit has not been reported (note_committed)
-                      "done": 0, "exact": True, "last_k": 0, "last_exact": True,
+                      # everything a forward and a commit change on the host (`_spec_host_end` and `_spec_host_commit` alone
+                      # write it, `host_state` copies it whole): flip, the operand slot the next forward writes; t_prev, the
+                      # tokens of the last forward; done / last_k, the tokens kept of the forwards before the last one / of
+                      # the last one — upper bounds, and flagged as such (exact / last_exact), while a device-side commit has
+                      # not been reported (note_committed)
+                      "host": {"flip": 0, "t_prev": 0, "done": 0, "exact": True, "last_k": 0, "last_exact": True},
                       "flush": {}, "cidx": None, "rows": {}, "lens_t": {}}
         self.speculating = True
 
@@ -358,14 +385,14 @@ class HybridMambaAttentionDynamicCache:
         """Operand views of T tokens in a layer's slot: which = 0 the one this forward writes, 1 the previous forward's."""
         d_in, G, N, H = self._mamba_dims
         B = self.ssm_states[layer_idx].shape[0]
-        sl = self._spec["slots"][layer_idx][self._spec["flip"] ^ which]
+        sl = self._spec["slots"][layer_idx][self._spec["host"]["flip"] ^ which]
         W = d_in + 2 * G * N + H
         return (sl["x"][:B * T * d_in].view(B, T, d_in), sl["B"][:B * G * T * N].view(B, G, T, N),
                 sl["C"][:B * G * T * N].view(B, G, T, N), sl["tail"][:B * T * W].view(B, T, W))
 
     def spec_prev_operands(self, layer_idx):
         """(x, dt, B, C) of the previous forward as the recurrence kernels take them, or None before the first one."""
-        T = self._spec["t_prev"]
+        T = self._spec["host"]["t_prev"]
         if T == 0:
             return None
         d_in, G, N, H = self._mamba_dims
@@ -376,23 +403,27 @@ class HybridMambaAttentionDynamicCache:
     # graph (GraphedSpecStep) runs it alone — the capture executed exactly these functions, so the two cannot drift apart
     def spec_check(self, T: int):
         """The host-side checks in front of a provisional forward of T tokens, eager or replayed."""
-        sp = self._spec
+        sp, h = self._spec, self._spec["host"]
         if T > sp["t_max"]:
             raise RuntimeError(f"speculation: {T} tokens in one forward, begin_speculation reserved t_max = {sp['t_max']}")
-        if sp["done"] + sp["last_k"] + T > sp["room"]:
+        if h["done"] + h["last_k"] + T > sp["room"]:
             raise RuntimeError("speculation: the key / value rows reserved by begin_speculation are used up")
 
     def _spec_host_end(self, T: int):
-        sp = self._spec
-        sp["done"] += sp["last_k"]
-        sp["exact"] = sp["exact"] and sp["last_exact"]
-        sp["flip"] ^= 1
-        sp["t_prev"], sp["last_k"], sp["last_exact"] = int(T), 0, True
+        h = self._spec["host"]
+        h["done"] += h["last_k"]
+        h["exact"] = h["exact"] and h["last_exact"]
+        h["flip"] ^= 1
+        h["t_prev"], h["last_k"], h["last_exact"] = int(T), 0, True
 
     def _spec_host_commit(self, k):
         """k: the host value, or None for a device-side commit nobody has reported yet (upper bound: every token)."""
-        sp = self._spec
-        sp["last_k"], sp["last_exact"] = (sp["t_prev"], False) if k is None else (int(k), True)
+        h = self._spec["host"]
+        h["last_k"], h["last_exact"] = (h["t_prev"], False) if k is None else (int(k), True)
+
+    def spec_parity(self) -> int:
+        """The operand slot the next forward writes: a captured step is the step of one parity (GraphedSpecStep)."""
+        return self._spec["host"]["flip"]
 
     def spec_replayed(self, T: int):
         """Host side of a REPLAYED step (forward + device-side commit), behind `spec_check(T)` in front of the launch: what
@@ -411,7 +442,7 @@ class HybridMambaAttentionDynamicCache:
     def spec_commit_conv(self, layer_idx):
         """conv state <- the last K columns of [state | the previous forward's pre-conv rows[:n_commit]]: a gather with a
         device index (nothing to do before the first forward)."""
-        T = self._spec["t_prev"]
+        T = self._spec["host"]["t_prev"]
         if T == 0:
             return
         cs = self.conv_states[layer_idx]
@@ -431,7 +462,7 @@ class HybridMambaAttentionDynamicCache:
         if not self.speculating:
             raise RuntimeError("commit: the cache is not in speculation mode")
         sp = self._spec
-        T = sp["t_prev"]
+        T = sp["host"]["t_prev"]
         if isinstance(k, torch.Tensor):
             kt = k.reshape(1).to(torch.int32).clamp(0, T)
             self._spec_host_commit(None)
@@ -448,7 +479,7 @@ class HybridMambaAttentionDynamicCache:
 
     def note_committed(self, k: int):
         """Host side of a device-side `commit(tensor)`: the value, once the caller has read it back."""
-        if not 0 <= int(k) <= self._spec["t_prev"]:
+        if not 0 <= int(k) <= self._spec["host"]["t_prev"]:
             raise ValueError("note_committed: k outside the last forward")
         self._spec_host_commit(k)
 
@@ -457,8 +488,8 @@ class HybridMambaAttentionDynamicCache:
         views to the committed length and free the slots: the cache is then what plain steps over the kept tokens leave."""
         if not self.speculating:
             return
-        sp = self._spec
-        if sp["t_prev"] > 0:
+        sp, h = self._spec, self._spec["host"]
+        if h["t_prev"] > 0:
             sp["cidx"] = sp["kidx"] + sp["n_commit"]
             for i, fl in sp["flush"].items():
                 self.spec_commit_conv(i)
@@ -466,15 +497,12 @@ class HybridMambaAttentionDynamicCache:
                                               fl["A"], dt_bias=fl["dt_bias"], dt_softplus=True, dt_limit=fl["dt_limit"],
                                               group_map=fl["group_map"])
         first = self.attention_layers[0]
-        if sp["exact"] and sp["last_exact"]:
-            done = sp["done"] + sp["last_k"]
+        if h["exact"] and h["last_exact"]:
+            done = h["done"] + h["last_k"]
         else:       # a device-side commit nobody reported: one read
             done = int(self._static_of[first][0]) - sp["base"][first]
         for i in self.attention_layers:
-            n = sp["base"][i] + done
-            kb, vb = self._kv_buf[i]
-            self._kv_len[i] = n
-            self.key_cache[i], self.value_cache[i] = kb[:, :n], vb[:, :n]
+            self._set_len(i, sp["base"][i] + done)
         self._static, self._static_of = {}, {}
         self.speculating, self._spec = False, None
 

@@ -427,6 +427,24 @@ int tv_gemv_bf16_fwd(const void* x, const void* W, const void* bias, void* y, in
                      int group_size, void* conv_state, const void* conv_weight, const void* conv_bias,
                      int conv_row0, int conv_channels, void* stream);
 
+/* The same product on 8-bit weights (half the bytes a token moves):
+ *   y[m][n] = bf16( w_scale[n] * sum_k f(x)[m][k] Q[n][k] + bias[n] ),
+ * Q (N, K) in e4m3 (OCP float8_e4m3fn, one byte a weight; ldw in elements = bytes), w_scale fp32 (N), any finite positive
+ * values.  x, bias, y, f (the four prologues, their rounding points) and the conv epilogue are tv_gemv_bf16_fwd's, fp32
+ * accumulation, the scale multiplies the finished sum once.  Where every scale is a power of two, diag(w_scale) Q is a
+ * bf16 matrix and this entry point and tv_gemv_bf16_fwd on that matrix differ by the order of the additions only.
+ * 1 <= M <= 4, K % 16 == 0, ldw % 16 == 0, W 16-byte aligned, M * K * 2 <= 128 KiB; anything else is TV_ERR_UNSUPPORTED
+ * or TV_ERR_BAD_ARG without a launch.  Nothing is read past byte K - 1 of a row of Q or past row N - 1.
+ * tv_gemv_fp8w_calls(): launches by this process (tests: a quantized product did not run on bf16).
+ * Purely additive: tv_abi_version() stays 13. */
+int tv_gemv_fp8w_fwd(const void* x, const void* W, const void* w_scale, const void* bias, void* y, int M, int N, int K,
+                     int64_t x_stride, int64_t ldw, int64_t y_stride, int prologue, const void* delta,
+                     int64_t delta_stride, void* sum_out, int64_t sum_stride, const void* norm_weight,
+                     int norm_weight_dtype, float eps, const void* gate, int64_t gate_stride,
+                     int group_size, void* conv_state, const void* conv_weight, const void* conv_bias,
+                     int conv_row0, int conv_channels, void* stream);
+int tv_gemv_fp8w_calls(void);
+
 /* The same product for the few-token forwards (a continuation or a speculative step of T tokens on one sequence:
  * torch.nn.Linear at 2 <= q_len <= 16), with the weights streamed once and the products on the matrix pipe:
  *   y[m][n] = sum_k f(x)[m][k] W[n][k] (+ bias[n]),   1 <= M <= 16, x / W / y bf16, fp32 accumulation, one rounding of y.

@@ -712,8 +712,10 @@ def gemv_takes(x: torch.Tensor, weight: torch.Tensor) -> bool:
             and weight.stride(0) % 8 == 0)
 
 
-def _linear_operands(name, x, weight, bias, delta, sum_out, norm_weight, eps, gate, group_size):
-    """The operand checks gemv_fused and linear_rows_fused share (`name`: the wrapper, for the messages).  Returns the
+def _linear_operands(name, x, weight, bias, delta, sum_out, norm_weight, eps, gate, group_size,
+                     w_dtype=torch.bfloat16, w_piece=8):
+    """The operand checks gemv_fused, gemv_fp8w_fused and linear_rows_fused share (`name`: the wrapper, for the messages;
+    `w_dtype`, `w_piece`: the weight dtype of the wrapper's entry point and the elements of its 16-byte piece).  Returns the
     (rows, K) view of x, in C order the arguments of tv_gemv_bf16_fwd / tv_linear_rows_bf16_fwd from `delta` to
     `group_size`, and the tensors those pointers belong to — `_rows2d` may have copied delta / gate, and the caller must
     hold the copies until the launch is queued."""
@@ -722,10 +724,10 @@ def _linear_operands(name, x, weight, bias, delta, sum_out, norm_weight, eps, ga
     x2 = _rows2d(x)
     if weight.dim() != 2 or weight.shape[1] != K:
         raise TimeViperHipError(f"{name}: weight {tuple(weight.shape)} against rows of {K}")
-    # the C ABI carries no weight dtype: anything but dense bf16 rows would be re-interpreted silently
-    if (x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.stride(1) != 1 or weight.stride(0) % 8
-            or K % 8):
-        raise TimeViperHipError(f"{name}: bf16 x and weight with dense rows of a multiple of 8 elements only "
+    # the C ABI carries no weight dtype: anything but dense rows of the entry point's own would be re-interpreted silently
+    if (x.dtype != torch.bfloat16 or weight.dtype != w_dtype or weight.stride(1) != 1 or weight.stride(0) % w_piece
+            or K % w_piece):
+        raise TimeViperHipError(f"{name}: bf16 x and {w_dtype} weight with dense rows of a multiple of {w_piece} elements only "
                                 f"(x {x.dtype}, weight {weight.dtype}, strides {tuple(weight.stride())}, K {K})")
     d2 = None if delta is None else _rows2d(delta)
     g2 = None if gate is None else _rows2d(gate)
@@ -745,6 +747,19 @@ def _linear_operands(name, x, weight, bias, delta, sum_out, norm_weight, eps, ga
                 int(group_size)), (d2, s2, g2)
 
 
+def _conv_operands(name, x, M, conv):
+    """The conv epilogue's operands of gemv_fused / gemv_fp8w_fused, checked: (state, weight, bias, row0, channels)."""
+    if conv is None:
+        return None, None, None, 0, 0
+    cst, cw, cb, row0 = conv
+    _gpu(cst, cw, cb)
+    nch = cst.shape[1]
+    if (cst.dtype != x.dtype or cw.dtype != x.dtype or not cst.is_contiguous() or not cw.is_contiguous()
+            or cst.shape != (M, nch, 4) or cw.shape != (nch, 4) or (cb is not None and (cb.dtype != x.dtype or not cb.is_contiguous()))):
+        raise TimeViperHipError(f"{name}: conv needs a contiguous (rows, C, 4) state and (C, 4) weight of x's dtype")
+    return cst, cw, cb, row0, nch
+
+
 def gemv_fused(x, weight, bias=None, prologue=GEMV_NONE, delta=None, sum_out=None, norm_weight=None, eps=0.0,
                gate=None, group_size=0, conv=None):
     """y = f(x) @ weight.T (+ bias) for 1..4 rows — the linear layers of a decode step (torch.nn.Linear at q_len 1) with
@@ -756,18 +771,81 @@ def gemv_fused(x, weight, bias=None, prologue=GEMV_NONE, delta=None, sum_out=Non
     x2, pro_args, held = _linear_operands("gemv_fused", x, weight, bias, delta, sum_out, norm_weight, eps, gate, group_size)
     (M, K), N = x2.shape, weight.shape[0]
     y = torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
-    cst = cw = cb = None
-    row0 = nch = 0
-    if conv is not None:
-        cst, cw, cb, row0 = conv
-        _gpu(cst, cw, cb)
-        nch = cst.shape[1]
-        if (cst.dtype != x.dtype or cw.dtype != x.dtype or not cst.is_contiguous() or not cw.is_contiguous()
-                or cst.shape != (M, nch, 4) or cw.shape != (nch, 4) or (cb is not None and (cb.dtype != x.dtype or not cb.is_contiguous()))):
-            raise TimeViperHipError("gemv_fused: conv needs a contiguous (rows, C, 4) state and (C, 4) weight of x's dtype")
+    cst, cw, cb, row0, nch = _conv_operands("gemv_fused", x, M, conv)
     check(_capi.lib().tv_gemv_bf16_fwd(
         _p(x2), _p(weight), _p(bias), _p(y), M, N, K, x2.stride(0), weight.stride(0), N, int(prologue),
         *pro_args, _p(cst), _p(cw), _p(cb), int(row0), int(nch), _stream()), "tv_gemv_bf16_fwd")
+    del held                # (alive up to here: see _linear_operands)
+    return y
+
+
+# ------------------------------------------------------------------- decode on e4m3 weights
+E4M3_MAX = 448.0
+
+
+def quantize_rows_e4m3(W: torch.Tensor):
+    """A bf16 (N, K) matrix as e4m3 bytes with one power-of-two fp32 scale per row: (w8 `torch.float8_e4m3fn` (N, K) with a
+    row stride that is a multiple of 16 bytes, scale (N,)), scale[n] = 2^e with 224 < amax_n / scale[n] <= 448 (an all-zero
+    row: 1), w8 = round-to-nearest-even of W / scale.  An e4m3 value times a power of two is a bf16 value, so the
+    dequantized matrix `dequantize_rows_e4m3(w8, scale)` is exact in bf16.  Plain torch (runs on the CPU too): not a hot path."""
+    if W.dim() != 2 or W.dtype != torch.bfloat16:
+        raise TimeViperHipError(f"quantize_rows_e4m3: a bf16 (N, K) matrix, not {W.dtype} {tuple(W.shape)}")
+    Wf = W.detach().float()
+    amax = Wf.abs().amax(dim=1)
+    if not bool(torch.isfinite(amax).all()):
+        raise TimeViperHipError("quantize_rows_e4m3: the matrix holds inf or NaN")
+    zero = amax == 0
+    safe = torch.where(zero, torch.full_like(amax, E4M3_MAX), amax)
+    scale = torch.exp2(torch.ceil(torch.log2(safe / E4M3_MAX)))
+    # log2 is not trusted at the boundaries: one step either way where the inequality fails (divisions by 2^e are exact)
+    scale = torch.where(safe / scale > E4M3_MAX, scale * 2, scale)
+    scale = torch.where(safe / scale <= E4M3_MAX / 2, scale / 2, scale)
+    q = (Wf / scale[:, None]).clamp_(-E4M3_MAX, E4M3_MAX)
+    N, Kd = W.shape
+    ld = (Kd + 15) // 16 * 16
+    buf = torch.zeros((N, ld), dtype=torch.float8_e4m3fn, device=W.device)
+    w8 = buf[:, :Kd]
+    w8.copy_(q.to(torch.float8_e4m3fn))
+    return w8, scale
+
+
+def dequantize_rows_e4m3(w8: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """diag(scale) w8 as bf16 (exact where the scales are powers of two)."""
+    return (w8.float() * scale[:, None].float()).to(torch.bfloat16)
+
+
+def gemv_fp8w_takes(x: torch.Tensor, w8: torch.Tensor) -> bool:
+    """Shapes tv_gemv_fp8w_fwd is written for: 1..4 rows of bf16 against an e4m3 (N, K) weight with K % 16 == 0 and
+    16-byte aligned rows, f(x) within 128 KiB of LDS."""
+    K = x.shape[-1]
+    rows = x.numel() // max(K, 1)
+    return (x.is_cuda and x.dtype == torch.bfloat16 and w8.dtype == torch.float8_e4m3fn and w8.dim() == 2
+            and w8.shape[1] == K and 1 <= rows <= 4 and K % 16 == 0 and rows * K * 2 <= 128 * 1024
+            and w8.stride(1) == 1 and w8.stride(0) % 16 == 0 and w8.data_ptr() % 16 == 0)
+
+
+def gemv_fp8w_calls() -> int:
+    """Launches of tv_gemv_fp8w_fwd by this process (tests: a quantized product did not run on its bf16 matrix)."""
+    return int(_capi.lib().tv_gemv_fp8w_calls())
+
+
+def gemv_fp8w_fused(x, w8, w_scale, bias=None, prologue=GEMV_NONE, delta=None, sum_out=None, norm_weight=None, eps=0.0,
+                    gate=None, group_size=0, conv=None):
+    """`gemv_fused` on 8-bit weights: y = (f(x) @ w8.T) * w_scale (+ bias) for 1..4 rows, w8 (N, K) `torch.float8_e4m3fn`
+    with K % 16 == 0 and 16-byte aligned rows, w_scale fp32 (N,) — the pair `quantize_rows_e4m3` returns.  Prologues,
+    rounding points and the conv epilogue are gemv_fused's; the scale multiplies the fp32 sum once."""
+    x2, pro_args, held = _linear_operands("gemv_fp8w_fused", x, w8, bias, delta, sum_out, norm_weight, eps, gate, group_size,
+                                          w_dtype=torch.float8_e4m3fn, w_piece=16)
+    (M, K), N = x2.shape, w8.shape[0]
+    _gpu(w_scale)
+    if w_scale.dtype != torch.float32 or not w_scale.is_contiguous() or w_scale.numel() != N:
+        raise TimeViperHipError(f"gemv_fp8w_fused: w_scale must be {N} contiguous fp32 entries (got {w_scale.dtype} "
+                                f"{tuple(w_scale.shape)})")
+    cst, cw, cb, row0, nch = _conv_operands("gemv_fp8w_fused", x, M, conv)
+    y = torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
+    check(_capi.lib().tv_gemv_fp8w_fwd(
+        _p(x2), _p(w8), _p(w_scale), _p(bias), _p(y), M, N, K, x2.stride(0), w8.stride(0), N, int(prologue),
+        *pro_args, _p(cst), _p(cw), _p(cb), int(row0), int(nch), _stream()), "tv_gemv_fp8w_fwd")
     del held                # (alive up to here: see _linear_operands)
     return y
 

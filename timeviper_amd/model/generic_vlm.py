@@ -354,7 +354,8 @@ class GenericTimeViperVLM(nn.Module):
         pick = (lambda logits: logits.argmax(-1)) if sampler is None else sampler.sample
         tok = pick(out.logits[:, -1])
         self.last_generate_stats = {"speculative": False, "steps": 0, "drafted": 0, "accepted": 0, "emitted": 0,
-                                    "graphed": False, "replays": 0, "graphs": 0, "capture_error": None}
+                                    "graphed": False, "replays": 0, "graphs": 0, "capture_error": None,
+                                    "fp8_weights": self._fp8_weights_on()}
         n_drafts = self._speculative_drafts(speculative, cache, max_new_tokens, sampled=sampler is not None)
         if n_drafts:
             history = [int(t) for t in prompt_ids.reshape(-1).tolist()]
@@ -379,6 +380,29 @@ class GenericTimeViperVLM(nn.Module):
         self.last_generate_stats.update(steps=fed, emitted=len(new_tokens), graphed=stepper is not None
                                         and stepper.graph is not None)
         return self._finish_generate(new_tokens, fed, cache, return_ids, return_cache)
+
+    # ------------------------------------------------------------------ decode on e4m3 weights
+    def quantize_llm_weights_e4m3(self) -> int:
+        """`NemotronHForCausalLM.quantize_weights_e4m3` of the language model: its linear weights rounded to e4m3 with
+        power-of-two row scales IN PLACE (the originals are gone), the 8-bit copies kept for the decode step's products.
+        Opt-in; every decode mode (plain, speculative, branched, sampled, graphed) then runs on them unchanged."""
+        llm = self.llm_backbone.llm
+        if not hasattr(llm, "quantize_weights_e4m3"):
+            raise NotImplementedError(f"e4m3 weights are implemented for the Nemotron-H hybrid only, not {type(llm).__name__}")
+        return llm.quantize_weights_e4m3()
+
+    def drop_llm_fp8_weights(self) -> None:
+        """Free the 8-bit copies (the rounded bf16 weights stay)."""
+        llm = self.llm_backbone.llm
+        if not hasattr(llm, "drop_fp8_weights"):
+            raise NotImplementedError(f"e4m3 weights are implemented for the Nemotron-H hybrid only, not {type(llm).__name__}")
+        llm.drop_fp8_weights()
+
+    def _fp8_weights_on(self) -> bool:
+        """Whether the decode products of this call read e4m3 copies: quantized, not dropped, TV_FP8W not 0, on the GPU."""
+        llm = self.llm_backbone.llm
+        return bool(getattr(llm, "has_fp8_weights", lambda: False)() and os.environ.get("TV_FP8W", "1") != "0"
+                    and self.device.type == "cuda")
 
     def _eos_set(self, eos_token_id) -> set:
         eos = self.eos_token_ids_to_use if eos_token_id is None else eos_token_id
@@ -545,7 +569,8 @@ class GenericTimeViperVLM(nn.Module):
                                              **sample))
                 steps += self.last_generate_stats["steps"]
                 graphed = graphed or bool(self.last_generate_stats["graphed"])
-            self.last_generate_stats = {"branched": False, "branches": B, "steps": steps, "graphed": graphed}
+            self.last_generate_stats = {"branched": False, "branches": B, "steps": steps, "graphed": graphed,
+                                        "fp8_weights": self._fp8_weights_on()}
             return results
         eos = self._eos_set(eos_token_id)
         if getattr(cache, "get_seq_length", None) and cache.get_seq_length() == 0:
@@ -592,7 +617,8 @@ class GenericTimeViperVLM(nn.Module):
                 new_tokens[b].append(int(nxt[b]))
                 done[b] = nxt[b] in eos or len(new_tokens[b]) >= max_new_tokens
         self.last_generate_stats = {"branched": True, "branches": B, "steps": steps,
-                                    "graphed": stepper is not None and stepper.graph is not None}
+                                    "graphed": stepper is not None and stepper.graph is not None,
+                                    "fp8_weights": self._fp8_weights_on()}
         return [self._result(torch.tensor([t], device=self.device), return_ids) for t in new_tokens]
 
     def _graphed_decode_step(self, cache, max_new_tokens, pdargs, sampler=None):

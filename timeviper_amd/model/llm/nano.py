@@ -559,8 +559,33 @@ def fused_route(model, hidden, cache, cache_position, output_hidden_states=False
     return route
 
 
+def fp8_copy(holder, params, x=None):
+    """The e4m3 copy (w8, scale) `quantize_weights_e4m3` left on `holder` for the matrix made of `params`, or None: no copy,
+    TV_FP8W=0 (read per call: bf16 without dropping anything), a copy whose key no longer matches its parameters (they
+    were rewritten or moved: that matrix runs on bf16, nothing is re-quantized silently) or, given x, a shape
+    tv_gemv_fp8w_fwd does not take."""
+    ent = getattr(holder, "_fp8w", None)
+    if ent is None or os.environ.get("TV_FP8W", "1") == "0" or ent[0] != K.param_key(params):
+        return None
+    if x is not None and not K.gemv_fp8w_takes(x, ent[1]):
+        return None
+    return ent[1], ent[2]
+
+
+def _gemv_product(lin, x, weight, bias, prologue, fp8=None, **kw):
+    """lin(x, weight, bias, prologue, ...), on the e4m3 copy `fp8` of the weight where `lin` is the decode step's
+    matrix-vector kernel and the copy's kernel takes the shape."""
+    if fp8 is not None and lin is K.gemv_fused and K.gemv_fp8w_takes(x, fp8[0]):
+        return K.gemv_fp8w_fused(x, fp8[0], fp8[1], bias, prologue, **kw)
+    return lin(x, weight, bias, prologue, **kw)
+
+
 def _linear(mod: nn.Linear, x: torch.Tensor, route: Optional[str] = None) -> torch.Tensor:
     """mod(x) on the kernel of `route` (`linear_route` of x) where that kernel takes the shapes."""
+    if route == "gemv":
+        q = fp8_copy(mod, (mod.weight,), x)
+        if q is not None:
+            return K.gemv_fp8w_fused(x, q[0], q[1], mod.bias)
     if route == "gemv" and K.gemv_takes(x, mod.weight):
         return K.gemv_fused(x, mod.weight, mod.bias)
     if route == "rows" and K.linear_rows_takes(x, mod.weight):
@@ -568,12 +593,14 @@ def _linear(mod: nn.Linear, x: torch.Tensor, route: Optional[str] = None) -> tor
     return mod(x)
 
 
-def _norm_linear(lin, hidden, delta, norm, weight, bias, **kw):
+def _norm_linear(lin, hidden, delta, norm, weight, bias, fp8=None, **kw):
     """A block's first product with its RMSNorm (+ the pending residual add, written to a new residual stream) in the
-    prologue of `lin` (K.gemv_fused / K.linear_rows_fused).  Returns (residual stream, product)."""
+    prologue of `lin` (K.gemv_fused / K.linear_rows_fused; `fp8`: the weight's e4m3 copy, `_gemv_product`).  Returns
+    (residual stream, product)."""
     new_hidden = torch.empty_like(hidden) if delta is not None else hidden
-    y = lin(hidden, weight, bias, K.GEMV_RMSNORM, delta=delta, sum_out=new_hidden if delta is not None else None,
-            norm_weight=norm.weight, eps=norm.variance_epsilon, **kw)
+    y = _gemv_product(lin, hidden, weight, bias, K.GEMV_RMSNORM, fp8, delta=delta,
+                      sum_out=new_hidden if delta is not None else None, norm_weight=norm.weight,
+                      eps=norm.variance_epsilon, **kw)
     return new_hidden, y
 
 
@@ -801,10 +828,12 @@ class NemotronHMamba2Mixer(nn.Module):
                     and conv_state.dtype == hidden.dtype and conv_state.is_contiguous() and w.is_contiguous()):
                 conv = (conv_state, w, self.conv1d.bias, self.intermediate_size)
         new_hidden, proj = _norm_linear(lin, hidden, delta, norm, self.in_proj.weight, self.in_proj.bias,
+                                        fp8=fp8_copy(self.in_proj, (self.in_proj.weight,)),
                                         **({} if conv is None else {"conv": conv}))
         gate, y = self._recur(cache_params, proj, conv_done=conv is not None)
-        out = lin(y, self.out_proj.weight, self.out_proj.bias, K.GEMV_GATED, norm_weight=self.norm.weight,
-                  eps=self.norm.variance_epsilon, gate=gate, group_size=self.norm.group_size)
+        out = _gemv_product(lin, y, self.out_proj.weight, self.out_proj.bias, K.GEMV_GATED,
+                            fp8_copy(self.out_proj, (self.out_proj.weight,)), norm_weight=self.norm.weight,
+                            eps=self.norm.variance_epsilon, gate=gate, group_size=self.norm.group_size)
         return new_hidden, out
 
 
@@ -829,8 +858,10 @@ class NemotronHMLP(nn.Module):
 
     def step_fused(self, lin, hidden, delta, norm, cache_params=None):
         """RMSNorm (+ residual add) inside up_proj, relu^2 inside down_proj — 2 launches (the cache is not used)."""
-        new_hidden, u = _norm_linear(lin, hidden, delta, norm, self.up_proj.weight, self.up_proj.bias)
-        return new_hidden, lin(u, self.down_proj.weight, self.down_proj.bias, K.GEMV_RELU2)
+        new_hidden, u = _norm_linear(lin, hidden, delta, norm, self.up_proj.weight, self.up_proj.bias,
+                                     fp8=fp8_copy(self.up_proj, (self.up_proj.weight,)))
+        return new_hidden, _gemv_product(lin, u, self.down_proj.weight, self.down_proj.bias, K.GEMV_RELU2,
+                                         fp8_copy(self.down_proj, (self.down_proj.weight,)))
 
 
 class NemotronHAttention(nn.Module):
@@ -913,7 +944,9 @@ class NemotronHAttention(nn.Module):
         the cache writes, split-KV attention, o_proj — one token: 4 launches + the cache writes, against 7."""
         B, T = hidden.shape[:2]
         nq, nkv = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
-        new_hidden, qkv = _norm_linear(lin, hidden, delta, norm, self._qkv_weight(), None)
+        # (the e4m3 copy of [q; k; v] is keyed by the three projections, as the bf16 concatenation is)
+        new_hidden, qkv = _norm_linear(lin, hidden, delta, norm, self._qkv_weight(), None,
+                                       fp8=fp8_copy(self, (self.q_proj.weight, self.k_proj.weight, self.v_proj.weight)))
         q, k, v = qkv.split([nq, nkv, nkv], dim=-1)
         q = q.view(B, T, self.num_heads, self.head_dim)
         k = k.view(B, T, self.num_key_value_heads, self.head_dim)
@@ -1218,6 +1251,63 @@ class NemotronHForCausalLM(nn.Module):
     def new_cache(self, batch_size=1, dtype=None, device=None):
         return HybridMambaAttentionDynamicCache(self.config, batch_size, dtype=dtype or self.dtype,
                                                 device=device or self.device)
+
+    # ------------------------------------------------------------------ decode on e4m3 weights
+    def _fp8_linears(self):
+        """(holder, parameters) of every matrix `quantize_weights_e4m3` covers: each nn.Linear of the blocks' mixers, and
+        lm_head unless it is tied to the embeddings.  Embeddings, norms, the conv and A / D / dt are never touched."""
+        out = [(m, (m.weight,)) for blk in self.backbone.layers for m in blk.mixer.modules() if isinstance(m, nn.Linear)]
+        emb = self.backbone.embeddings.weight
+        head = self.lm_head.weight
+        if head is not emb and head.data_ptr() != emb.data_ptr():
+            out.append((self.lm_head, (head,)))
+        return out
+
+    @torch.no_grad()
+    def quantize_weights_e4m3(self) -> int:
+        """Round every linear weight of the blocks (and an untied lm_head) to e4m3 with one power-of-two scale per output
+        row (K.quantize_rows_e4m3), IN PLACE: the bf16 weight becomes the dequantized matrix — exact in bf16 — and the
+        (e4m3, scale) pair is kept beside it for the decode step's 1..4-row products (tv_gemv_fp8w_fwd: the same numbers
+        at half the bytes).  Every other route — prefill, continuation, the speculative verify forward, the rows kernel,
+        the library GEMM — computes with the rounded bf16 weights on the kernels it uses anyway, so the model stays one
+        model.  The original weights are gone: reload to get them back.  Returns the number of matrices quantized."""
+        pairs = self._fp8_linears()
+        for mod, (w,) in pairs:
+            if w.dtype != torch.bfloat16 or w.dim() != 2:
+                raise TypeError(f"quantize_weights_e4m3: bf16 matrices only (found {w.dtype} {tuple(w.shape)}); "
+                                "convert the model with .bfloat16() first")
+        for mod, (w,) in pairs:
+            w8, scale = K.quantize_rows_e4m3(w)
+            w.copy_(K.dequantize_rows_e4m3(w8, scale))
+            mod._fp8w = (K.param_key((w,)), w8, scale)         # (the key AFTER the write: it bumps the version)
+        for blk in self.backbone.layers:
+            att = blk.mixer
+            if isinstance(att, NemotronHAttention) and not self.config.attention_bias:
+                # the decode token's single [q; k; v] product: scales are per row, so the copy is the concatenation
+                projs = (att.q_proj, att.k_proj, att.v_proj)
+                w8 = torch.cat([p._fp8w[1] for p in projs], dim=0).contiguous()
+                scale = torch.cat([p._fp8w[2] for p in projs], dim=0).contiguous()
+                att._fp8w = (K.param_key(tuple(p.weight for p in projs)), w8, scale)
+        self._fp8_quantized = True
+        return len(pairs)
+
+    def drop_fp8_weights(self) -> None:
+        """Free the e4m3 copies; the rounded bf16 weights stay (the decode step streams them again)."""
+        for m in self.modules():
+            if getattr(m, "_fp8w", None) is not None:
+                m._fp8w = None
+        self._fp8_quantized = False
+
+    def has_fp8_weights(self) -> bool:
+        return bool(getattr(self, "_fp8_quantized", False))
+
+    def _apply(self, fn, *a, **kw):
+        self.drop_fp8_weights()          # (.to() / .bfloat16(): the parameters move or change, the copies would not follow)
+        return super()._apply(fn, *a, **kw)
+
+    def load_state_dict(self, *a, **kw):
+        self.drop_fp8_weights()
+        return super().load_state_dict(*a, **kw)
 
     def set_pdrop_args(self, **kwargs):
         for key, value in kwargs.items():
